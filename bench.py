@@ -51,6 +51,36 @@ def parse_strategy(text, world):
     return st
 
 
+_DUMP_SAMPLE = 4096   # elements kept per parameter tensor
+
+
+def dump_outputs(out_dir, loss, params):
+    """Write what the last timed step produced as float32 .npy files:
+    loss.npy (the value step() returned) and params_sample.npy (the
+    updated weights, a fixed seeded sample of _DUMP_SAMPLE elements per
+    tensor, concatenated in state-dict order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if loss is not None:
+        np.save(os.path.join(out_dir, "loss.npy"),
+                loss.detach().float().cpu().numpy().reshape(-1))
+    chunks = []
+    gen = torch.Generator()
+    gen.manual_seed(20240229)
+    for data in params().values():
+        if data is None:
+            continue
+        flat = data.detach().reshape(-1)
+        n = flat.numel()
+        if n > _DUMP_SAMPLE:
+            idx = torch.randint(0, n, (_DUMP_SAMPLE,), generator=gen)
+            flat = flat[idx.to(flat.device)]
+        chunks.append(flat.float().cpu())
+    if chunks:
+        np.save(os.path.join(out_dir, "params_sample.npy"),
+                torch.cat(chunks).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -66,6 +96,14 @@ def main():
     ap.add_argument("--capture", default="auto")
     ap.add_argument("--allow-cpu", action="store_true",
                     help="CI smoke only: run the same code path on CPU/gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "computed (loss, seeded sample of the updated "
+                         "parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; the plain "
+                         "run already does only what the headline figure "
+                         "needs, so today this adds nothing")
     args = ap.parse_args()
 
     if args.capture != "auto":
@@ -78,6 +116,7 @@ def main():
     from hetu_amd.engine.trainer import Trainer
     from hetu_amd.models.gpt import (GPT_CONFIGS, build_gpt_pipeline_stage,
                                      build_gpt_train_graph)
+    from hetu_amd.nn import init
     from hetu_amd.nn.parallel import ParallelSpec
     from hetu_amd.parallel.comm import comm_backend
     from hetu_amd.galvatron.cost_model import ModelShape
@@ -132,9 +171,15 @@ def main():
         # dp-only steady state: micro-batches fold into one captured step
         # of batch B*num_mb when no pipeline is involved
         eff_B = B * num_mb
-        g, h = build_gpt_train_graph(cfg, micro_batch=eff_B, seq_len=S_loc,
-                                     dtype=torch.bfloat16, lr=1e-4,
-                                     spec=spec, zero=st.zero)
+        # same weights as a plain build, drawn on a thread pool and copied
+        # to the device as they complete: the serial draws alone take most
+        # of a minute at 7B
+        g, h = init.build_with_pooled_draws(
+            lambda: build_gpt_train_graph(cfg, micro_batch=eff_B,
+                                          seq_len=S_loc,
+                                          dtype=torch.bfloat16, lr=1e-4,
+                                          spec=spec, zero=st.zero),
+            device=device)
         trainer = Trainer(g, h, device)
         pool = [torch.randint(0, cfg.vocab, (eff_B, S_loc), device=device)
                 for _ in range(4)]
@@ -145,6 +190,7 @@ def main():
             return trainer.step({h["input_ids"]: pool[i % 4],
                                  h["labels"]: lpool[i % 4]})
         capture_on = lambda: trainer._cuda_graph is not None  # noqa: E731
+        dump_params = lambda: h["model"].state_dict()  # noqa: E731
     else:
         from hetu_amd.parallel.pipeline import PipelineRunner, PipelineSpec
         pspec = PipelineSpec(pp=st.pp, dp=st.dp, tp=st.tp)
@@ -171,6 +217,9 @@ def main():
         def step_fn(i):
             return runner.step(mbs_pool[i % 2])
         capture_on = lambda: False  # noqa: E731
+        # a pipeline rank holds one stage; only the step's return value
+        # (mean loss, last stage only) is dumped
+        dump_params = dict
 
     loss = None
     for i in range(args.warmup):
@@ -193,6 +242,9 @@ def main():
         et = torch.tensor([elapsed], device=device)
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
         elapsed = et.item()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, dump_params)
 
     ms_per_step = elapsed / args.steps * 1000
     tokens_per_step = global_batch * S

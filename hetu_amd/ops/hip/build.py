@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 import sysconfig
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -51,6 +52,13 @@ def _torch_paths():
     return inc, lib, abi
 
 
+def _usable_cpus() -> int:
+    try:
+        return len(os.sched_getaffinity(0))
+    except AttributeError:
+        return os.cpu_count() or 1
+
+
 def build(verbose: bool = True) -> str:
     inc, libdir, abi = _torch_paths()
     py_inc = sysconfig.get_paths()["include"]
@@ -75,21 +83,31 @@ def build(verbose: bool = True) -> str:
         # make it a hard error
         "-Werror=return-type",
     ] + [f"-I{p}" for p in inc] + [f"-I{py_inc}", f"-I{HERE}"]
+    stale = []
     for src in srcs:
         base = os.path.basename(src).rsplit(".", 1)[0]
         obj = os.path.join(HERE, ".build", base + ".o")
+        objs.append(obj)
         # skip if up to date
         if (os.path.exists(obj)
                 and os.path.getmtime(obj) > os.path.getmtime(src)
                 and os.path.getmtime(obj) > os.path.getmtime(
                     os.path.join(HERE, "common.h"))):
-            objs.append(obj)
             continue
-        cmd = ["hipcc", "-c", src, "-o", obj] + common_flags
+        stale.append((src, obj))
+
+    def compile_one(job):
+        src, obj = job
         if verbose:
-            print("[hetu_amd build]", os.path.basename(src))
-        subprocess.run(cmd, check=True)
-        objs.append(obj)
+            print("[hetu_amd build]", os.path.basename(src), flush=True)
+        subprocess.run(["hipcc", "-c", src, "-o", obj] + common_flags,
+                       check=True)
+
+    # the translation units are independent; one hipcc per core (MAX_JOBS
+    # overrides, as for torch extensions) instead of 22 in a row
+    jobs = int(os.environ.get("MAX_JOBS", 0)) or min(16, _usable_cpus())
+    with ThreadPoolExecutor(max(1, jobs)) as pool:
+        list(pool.map(compile_one, stale))
     link = ["hipcc", "-shared", "-fPIC", "-o", out] + objs + [
         f"-L{libdir}", "-ltorch", "-ltorch_cpu", "-lc10",
         "-ltorch_python", "-lamdhip64", "-lhipblaslt",

@@ -49,6 +49,64 @@ def test_bench_ws2_pp2():
     assert out["value"] > 0
 
 
+def _run_ws1(extra):
+    p = subprocess.run(
+        [sys.executable, BENCH, "--allow-cpu", "--model", "gpt-tiny",
+         "--gpus", "1", "--steps", "3", "--warmup", "2",
+         "--seq-len", "32", "--global-batch", "4"] + extra,
+        capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, f"{p.stdout}\n{p.stderr}"
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's loss and parameter
+    sample as float32 .npy, identical from run to run; --steps sets the
+    timed step count and --full keeps the result line's schema."""
+    import numpy as np
+    outs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        line = _run_ws1(["--dump-outputs", str(d)] + extra)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert k in line
+        files = sorted(f.name for f in d.iterdir())
+        assert files == ["loss.npy", "params_sample.npy"]
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert np.float32(line["loss"]) == arrs["loss.npy"][0]
+        assert np.isfinite(arrs["params_sample.npy"]).all()
+        outs.append(arrs)
+    for f in outs[0]:
+        np.testing.assert_array_equal(outs[0][f], outs[1][f])
+
+
+def test_pooled_draws_match_serial_build():
+    """bench.py builds the model through init.build_with_pooled_draws:
+    every weight must be bit-identical to the plain serial build."""
+    import torch
+    from hetu_amd.models.gpt import GPT_CONFIGS, build_gpt_train_graph
+    from hetu_amd.nn import init
+
+    def build():
+        return build_gpt_train_graph(GPT_CONFIGS["gpt-tiny"], micro_batch=2,
+                                     seq_len=32, dtype=torch.bfloat16)
+
+    serial_normal = init.normal
+    _, h_ref = build()
+    g, h = init.build_with_pooled_draws(build, workers=3,
+                                        device=torch.device("cpu"))
+    assert init.normal is serial_normal
+    ref, got = h_ref["model"].state_dict(), h["model"].state_dict()
+    assert list(ref) == list(got) and len(ref) > 4
+    for k in ref:
+        assert torch.equal(ref[k], got[k]), k
+
+
 def test_bench_ws8_auto():
     """8-rank gloo smoke of the exact round-end N=8 invocation shape:
     auto search at ws=8, strategy broadcast to all ranks, whole-job

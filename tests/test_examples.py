@@ -94,11 +94,11 @@ def test_hetero_driver_three_ranks():
     assert any("[pipe 1]" in o for o in outs)
 
 
-def test_elastic_driver_kill_one():
+def test_elastic_driver_kill_one(tmp_path):
     p = _run(["examples/elastic/elastic_train.py", "--world", "3",
               "--die-rank", "2", "--die-at", "2", "--steps", "5",
               "--kv-port", "29785"],
-             {"CKPT_DIR": "/tmp/elastic_demo_ckpt"}, timeout=400)
+             {"CKPT_DIR": str(tmp_path / "elastic_demo_ckpt")}, timeout=400)
     assert p.returncode == 0, p.stderr
     assert "rank 2 exited rc=17" in p.stdout
     assert '"final_world": 2' in p.stdout
