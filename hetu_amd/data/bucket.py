@@ -9,7 +9,7 @@ cu_seqlens).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -111,6 +111,67 @@ class Bucket:
                 out[r, b, :len(row)] = row
                 rank_cus[r].append(torch.tensor(rcu, dtype=torch.int32))
         return out, rank_cus
+
+
+def packed_feed(tokens: torch.Tensor, cu_seqlens: torch.Tensor,
+                max_segments: int, pad_token: int = 0,
+                ignore_index: int = -100,
+                seq_lens: Optional[Sequence[int]] = None
+                ) -> Dict[str, torch.Tensor]:
+    """Feed tensors of the packed Llama graph (build_llama_train_graph(...,
+    packed=True)) from ONE packed bin: `tokens` is a row of
+    Bucket.pack_data() ([T]) and `cu_seqlens` its offsets.  Pure host code.
+
+    Returns a dict of
+      input_ids    int64 [T]   the row itself (reshape to the graph's
+                               [micro_batch, seq_len] placeholder);
+      cu_seqlens   int32 [max_segments + 1]; a tail that pack_data left
+                   uncovered is closed as one more segment of its own so
+                   cu[-1] == T (every row then belongs to a segment and
+                   gets a defined attention output); unused entries repeat
+                   T, i.e. zero-length segments;
+      position_ids int64 [T]   restarting at 0 at every offset;
+      labels       int64 [T]   next-token labels: tokens[t + 1], and
+                   ignore_index at the last token of every segment (its
+                   successor is padding or another sequence) and on every
+                   pad position.
+
+    Segments are alignment-padded, so a sequence's real length is not in
+    cu_seqlens: pass `seq_lens` (real length per segment, in cu order) to
+    be exact; without it the trailing run of `pad_token` in a segment
+    counts as its padding (a sequence that really ends in pad_token loses
+    those labels)."""
+    tokens = tokens.reshape(-1).to(torch.int64)
+    T = tokens.numel()
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    assert cu and cu[0] == 0 and cu[-1] <= T and \
+        all(a <= b for a, b in zip(cu[:-1], cu[1:])), f"bad cu_seqlens {cu}"
+    n_real = len(cu) - 1
+    if seq_lens is not None:
+        assert len(seq_lens) == n_real
+    if cu[-1] < T:
+        cu.append(T)                    # the uncovered tail: all padding
+    assert len(cu) - 1 <= max_segments, \
+        f"{len(cu) - 1} segments > max_segments={max_segments}"
+    position_ids = torch.empty(T, dtype=torch.int64)
+    labels = torch.full((T,), ignore_index, dtype=torch.int64)
+    for i, (s0, s1) in enumerate(zip(cu[:-1], cu[1:])):
+        position_ids[s0:s1] = torch.arange(s1 - s0)
+        if i >= n_real:
+            continue
+        if seq_lens is not None:
+            n = int(seq_lens[i])
+            assert 0 <= n <= s1 - s0
+        else:
+            n = s1 - s0
+            while n > 0 and int(tokens[s0 + n - 1]) == pad_token:
+                n -= 1
+        if n > 1:
+            labels[s0:s0 + n - 1] = tokens[s0 + 1:s0 + n]
+    cu += [T] * (max_segments + 1 - len(cu))
+    return {"input_ids": tokens,
+            "cu_seqlens": torch.tensor(cu, dtype=torch.int32),
+            "position_ids": position_ids, "labels": labels}
 
 
 def bucketize(seqs: Sequence[torch.Tensor], boundaries: Sequence[int],

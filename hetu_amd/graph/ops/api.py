@@ -392,10 +392,14 @@ def fused_mlp(x, wfc, b1, wproj, b2=None):
                          {"with_b2": b2 is not None}).output()
 
 
-def varlen_attention(q, k, v, cu_seqlens, causal=True, scale=None):
-    """Packed-varlen attention: q/k/v [T, H, D], cu_seqlens [n+1]."""
+def varlen_attention(q, k, v, cu_seqlens, causal=True, scale=None,
+                     max_seqlen=None):
+    """Packed-varlen attention: q/k/v [T, H, D], cu_seqlens [n+1].
+    max_seqlen: optional launch-grid hint for forward and backward; must
+    be >= the longest segment (a too-small value silently drops rows)."""
     return _cg().make_op(N.VarlenAttentionOp(), [q, k, v, cu_seqlens],
-                         {"causal": causal, "scale": scale}).output()
+                         {"causal": causal, "scale": scale,
+                          "max_seqlen": max_seqlen}).output()
 
 
 def attention(q, k, v, causal=True, scale=None):

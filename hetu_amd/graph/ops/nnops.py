@@ -628,7 +628,9 @@ class FusedQKVAttentionGradOp(OpInterface):
 
 class VarlenAttentionOp(OpInterface):
     """Packed-varlen flash attention: q/k/v [T, H, D] + cu_seqlens [n+1]
-    (reference ParallelAttention.cc packed path)."""
+    (reference ParallelAttention.cc packed path).  attrs: causal, scale,
+    max_seqlen (optional grid hint, >= the longest segment; shared with
+    the grad op)."""
     type = "VarlenAttention"
 
     def infer_meta(self, attrs, inputs):
@@ -642,7 +644,8 @@ class VarlenAttentionOp(OpInterface):
         o, lse = F.varlen_attention_fwd(inputs[0], inputs[1], inputs[2],
                                         inputs[3],
                                         op.attrs.get("causal", True),
-                                        op.attrs.get("scale"))
+                                        op.attrs.get("scale"),
+                                        op.attrs.get("max_seqlen"))
         return [o, lse]
 
     def gradient(self, op, g):
@@ -667,7 +670,8 @@ class VarlenAttentionGradOp(OpInterface):
         dout, q, k, v, out, lse, cu = inputs
         return list(F.varlen_attention_bwd(dout, q, k, v, out, lse, cu,
                                            op.attrs.get("causal", True),
-                                           op.attrs.get("scale")))
+                                           op.attrs.get("scale"),
+                                           op.attrs.get("max_seqlen")))
 
 
 class FusedMLPOp(OpInterface):

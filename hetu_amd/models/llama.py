@@ -87,10 +87,15 @@ class LlamaAttention(Module):
             name=f"{p}.wo", init_std=proj_std)
         self.cos, self.sin = cos, sin
 
-    def forward(self, x, B, S):
+    def forward(self, x, B, S, packed=None):
+        """packed: None, or (cu_seqlens, cos_tok, sin_tok) — the [B, S]
+        tokens are then one packed row of T = B*S tokens whose segments
+        attend only within themselves (see LlamaLMHeadModel)."""
         spec, cfg = self.spec, self.cfg
         hl, kl, dh = self.h_local, self.kv_local, self.dh
         qkv = self.wqkv(x)                       # [B,S,(h+2kv)*dh / tp]
+        if packed is not None:
+            return self.wo(self._packed_attention(qkv, B, S, packed))
         if spec.cp == 1 and dh == 128 and os.environ.get(
                 "HETU_AMD_FUSED_ATTN", "1") == "1":
             # fused path: in-place RoPE on the q|k sections + strided
@@ -120,6 +125,28 @@ class LlamaAttention(Module):
                        ds=spec._ds({0: spec.dp, 1: spec.cp, 2: spec.tp},
                                    [0, 1, 2]))
         return self.wo(o)
+
+
+    def _packed_attention(self, qkv, B, S, packed):
+        """Packed-varlen path: q/k/v sliced straight to [T, h, dh] (the
+        layout rope and ht.varlen_attention take — no transposes), per-token
+        rotary tables, one varlen attention over all segments."""
+        spec = self.spec
+        hl, kl, dh = self.h_local, self.kv_local, self.dh
+        cu, cos_t, sin_t = packed
+        T = B * S
+        ds_tok = spec._ds({0: spec.dp, 1: spec.tp}, [0, 1])
+        q = ht.reshape(ht.slice_(qkv, 2, 0, hl * dh), (T, hl, dh),
+                       ds=ds_tok)
+        k = ht.reshape(ht.slice_(qkv, 2, hl * dh, kl * dh), (T, kl, dh),
+                       ds=ds_tok)
+        v = ht.reshape(ht.slice_(qkv, 2, (hl + kl) * dh, kl * dh),
+                       (T, kl, dh), ds=ds_tok)
+        q = ht.rotary(q, cos_t, sin_t)
+        k = ht.rotary(k, cos_t, sin_t)
+        o = ht.varlen_attention(q, k, v, cu, causal=True)
+        return ht.reshape(o, (B, S, hl * dh),
+                          ds=spec._ds({0: spec.dp, 2: spec.tp}, [0, 2]))
 
 
 class LlamaMLP(Module):
@@ -154,12 +181,12 @@ class LlamaBlock(Module):
                                    name=f"l{layer_idx}.ln2")
         self.mlp = LlamaMLP(cfg, spec, layer_idx, dtype)
 
-    def forward(self, x, B, S):
-        x = ht.add(x, self.attn(self.ln1(x), B, S))
+    def forward(self, x, B, S, packed=None):
+        x = ht.add(x, self.attn(self.ln1(x), B, S, packed))
         x = ht.add(x, self.mlp(self.ln2(x)))
         return x
 
-    def forward_chain(self, x, delta, B, S):
+    def forward_chain(self, x, delta, B, S, packed=None):
         """Pre-norm chain with the residual add fused into each RMSNorm
         (FusedAddRMSOp) — see GPTBlock.forward_chain."""
         if delta is None:
@@ -167,25 +194,44 @@ class LlamaBlock(Module):
         else:
             y1, s1 = ht.fused_add_rms(x, delta, self.ln1.weight,
                                       self.ln1.eps)
-        a = self.attn(y1, B, S)
+        a = self.attn(y1, B, S, packed)
         y2, s2 = ht.fused_add_rms(s1, a, self.ln2.weight, self.ln2.eps)
         return s2, self.mlp(y2)
 
 
 class LlamaLMHeadModel(Module):
     """Builds ops in the current graph; forward(input_ids, labels) ->
-    (loss, logits)."""
+    (loss, logits).
+
+    packed=True: the [micro_batch, seq_len] input is ONE packed row of
+    T = micro_batch * seq_len tokens holding up to max_segments sequences
+    back to back.  forward() then also takes cu_seqlens (int32
+    [max_segments + 1], unused entries repeating the last offset) and
+    position_ids (int64 [T], restarting at 0 in every segment): RoPE uses
+    the per-token table rows and attention runs as ht.varlen_attention,
+    so no token sees another segment.  All shapes are fixed, which keeps
+    the step graph-capturable.  The loss stays reduce_mean over all T
+    tokens, ignore_index (-100) labels contributing 0 — i.e. the sum of
+    the per-token losses divided by T, not by the number of real labels.
+    Packed mode does not combine with context parallelism."""
 
     def __init__(self, cfg: LlamaConfig, spec: Optional[ParallelSpec] = None,
                  micro_batch: int = 1, seq_len: int = 128,
-                 dtype=torch.bfloat16, recompute: bool = False):
+                 dtype=torch.bfloat16, recompute: bool = False,
+                 packed: bool = False, max_segments: int = 64):
         super().__init__()
         spec = spec or ParallelSpec()
         self.cfg, self.spec = cfg, spec
         self.recompute = recompute
         self.B, self.S = micro_batch, seq_len
         self.dtype = dtype
-        cos_d, sin_d = rope_tables(cfg, seq_len, torch.float32,
+        self.packed, self.max_segments = packed, max_segments
+        if packed:
+            assert spec.cp == 1, "packed mode does not support cp > 1"
+        # packed: a segment may span the whole row, so positions run to T
+        cos_d, sin_d = rope_tables(cfg,
+                                   micro_batch * seq_len if packed
+                                   else seq_len, torch.float32,
                                    offset=spec.my_cp_index() * seq_len)
         self.cos = ht.variable(cos_d, name="rope.cos", requires_grad=False,
                                ds=spec.ds_weight_dup(),
@@ -205,9 +251,17 @@ class LlamaLMHeadModel(Module):
             cfg.hidden, cfg.vocab, spec, bias=False, dtype=dtype,
             name="lm_head", init_std=cfg.init_std)
 
-    def forward(self, input_ids, labels=None):
+    def forward(self, input_ids, labels=None, cu_seqlens=None,
+                position_ids=None):
         import contextlib
         B, S, cfg, spec = self.B, self.S, self.cfg, self.spec
+        pk = None
+        if self.packed:
+            assert cu_seqlens is not None and position_ids is not None, \
+                "packed mode needs cu_seqlens and position_ids"
+            # per-token rotary tables [T, dh/2], shared by every layer
+            pk = (cu_seqlens, ht.embedding(self.cos, position_ids),
+                  ht.embedding(self.sin, position_ids))
         x = self.wte(input_ids)
         g = x.graph
         import os as _os
@@ -219,9 +273,9 @@ class LlamaLMHeadModel(Module):
                 else contextlib.nullcontext()
             with cm:
                 if fused_ln:
-                    x, delta = blk.forward_chain(x, delta, B, S)
+                    x, delta = blk.forward_chain(x, delta, B, S, pk)
                 else:
-                    x = blk(x, B, S)
+                    x = blk(x, B, S, pk)
         if fused_ln and delta is not None:
             x, _ = ht.fused_add_rms(x, delta, self.lnf.weight,
                                     self.lnf.eps)
@@ -383,8 +437,16 @@ def build_llama_train_graph(cfg: LlamaConfig, micro_batch: int, seq_len: int,
                             dtype=torch.bfloat16, lr: float = 1e-4,
                             spec: Optional[ParallelSpec] = None,
                             graph: Optional[DefineAndRunGraph] = None,
-                            zero: bool = False, recompute: bool = False
+                            zero: bool = False, recompute: bool = False,
+                            packed: bool = False, max_segments: int = 64
                             ) -> (DefineAndRunGraph, Dict):
+    """packed=True builds the packed-varlen training graph (see
+    LlamaLMHeadModel): the handles then also hold the `cu_seqlens`
+    (int32 [max_segments + 1]) and `position_ids` (int64 [T]) placeholders;
+    data.bucket.packed_feed produces all four feed tensors from one packed
+    bin.  The loss is the mean over all T = micro_batch * seq_len tokens,
+    ignored labels counting as 0.  packed=False builds exactly the graph
+    it always did."""
     g = graph or DefineAndRunGraph("llama_train")
     spec = spec or ParallelSpec()
     push_graph(g)
@@ -396,9 +458,20 @@ def build_llama_train_graph(cfg: LlamaConfig, micro_batch: int, seq_len: int,
         labels = ht.placeholder((micro_batch * seq_len,), dtype=torch.int64,
                                 name="labels", ds=spec.ds_tokens(0),
                                 device_group=spec.device_group)
+        extra = {}
+        if packed:
+            # every rank feeds the offsets / positions of its own row
+            extra["cu_seqlens"] = ht.placeholder(
+                (max_segments + 1,), dtype=torch.int32, name="cu_seqlens",
+                ds=spec.ds_weight_dup(), device_group=spec.device_group)
+            extra["position_ids"] = ht.placeholder(
+                (micro_batch * seq_len,), dtype=torch.int64,
+                name="position_ids", ds=spec.ds_tokens(0),
+                device_group=spec.device_group)
         model = LlamaLMHeadModel(cfg, spec, micro_batch, seq_len, dtype,
-                                 recompute=recompute)
-        loss, logits = model(input_ids, labels)
+                                 recompute=recompute, packed=packed,
+                                 max_segments=max_segments)
+        loss, logits = model(input_ids, labels, **extra)
         loss_report = loss
         if spec.num_devices > 1:
             loss_report = ht.comm(
@@ -408,6 +481,7 @@ def build_llama_train_graph(cfg: LlamaConfig, micro_batch: int, seq_len: int,
         train_op = opt.minimize(loss)
     finally:
         pop_graph()
-    return g, {"input_ids": input_ids, "labels": labels,
-               "loss": loss_report, "logits": logits, "train_op": train_op,
-               "optimizer": opt, "model": model}
+    return g, dict({"input_ids": input_ids, "labels": labels,
+                    "loss": loss_report, "logits": logits,
+                    "train_op": train_op, "optimizer": opt, "model": model},
+                   **extra)

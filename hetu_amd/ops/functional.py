@@ -732,13 +732,17 @@ def fused_qkv_attention_bwd(dout, qkv, out, lse, n_head: int,
 
 
 def varlen_attention_fwd(q, k, v, cu_seqlens, causal: bool = True,
-                         scale: Optional[float] = None):
+                         scale: Optional[float] = None,
+                         max_seqlen: Optional[int] = None):
     """Packed-varlen attention (reference ParallelAttention.cc packed
     path / FlashAttention.cu mha_varlen_fwd): q/k/v [T, H, D] with
     cu_seqlens [n+1] delimiting the packed sequences; each segment attends
     only within itself.  On GPU (D=128, no GQA mismatch constraint): ONE
     kernel launch with device-side cu offsets — no host loop, no
     `.tolist()` sync; blocks beyond a segment's tiles exit early.
+    max_seqlen (optional) only shrinks the launch grid: None sizes it by
+    T; a value must be >= the longest segment — a too-small value
+    SILENTLY drops the rows past it (they are never computed).
     Returns (out [T, H, D], lse [H, T])."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
@@ -746,8 +750,8 @@ def varlen_attention_fwd(q, k, v, cu_seqlens, causal: bool = True,
     if _use_hip("varlen", q) and D == 128:
         cu32 = cu_seqlens.to(device=q.device, dtype=torch.int32)
         o, lse = ext().flash_attn_varlen_fwd(
-            q.contiguous(), k.contiguous(), v.contiguous(), cu32, T,
-            causal, scale)
+            q.contiguous(), k.contiguous(), v.contiguous(), cu32,
+            T if max_seqlen is None else int(max_seqlen), causal, scale)
         return o, lse
     out = torch.empty_like(q)
     lse = torch.empty(H, T, dtype=torch.float32, device=q.device)
@@ -767,12 +771,28 @@ def varlen_attention_fwd(q, k, v, cu_seqlens, causal: bool = True,
 
 def varlen_attention_bwd(dout, q, k, v, out, lse, cu_seqlens,
                          causal: bool = True,
-                         scale: Optional[float] = None):
+                         scale: Optional[float] = None,
+                         max_seqlen: Optional[int] = None):
+    """Backward of varlen_attention_fwd -> (dq, dk, dv), packed like
+    q/k/v.  On GPU (D=128): three launches (delta, dq, dkv) over all
+    segments with device-side cu offsets — no host sync, so a packed
+    step can be hipGraph-captured.  Rows that belong to no segment
+    (t >= cu[-1]) come back ZERO on every path.  max_seqlen: see
+    varlen_attention_fwd (too small silently drops rows)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    dq = torch.empty_like(q)
-    dk = torch.empty_like(k)
-    dv = torch.empty_like(v)
+    T, H, D = q.shape
+    if _use_hip("varlen", q) and D == 128:
+        cu32 = cu_seqlens.to(device=q.device, dtype=torch.int32)
+        dq, dk, dv = ext().flash_attn_varlen_bwd(
+            dout.contiguous(), q.contiguous(), k.contiguous(),
+            v.contiguous(), out.contiguous(), lse.contiguous(), cu32,
+            T if max_seqlen is None else int(max_seqlen), causal, scale)
+        return dq, dk, dv
+    # CPU / other-D / HETU_AMD_TORCH_FALLBACK=varlen: per-segment loop
+    dq = torch.zeros_like(q)
+    dk = torch.zeros_like(k)
+    dv = torch.zeros_like(v)
     cu = cu_seqlens.tolist()
     for s0, s1 in zip(cu[:-1], cu[1:]):
         if s1 <= s0:

@@ -135,14 +135,18 @@ DEV int kswz_row(int row, int byte_in_row) {
 // ===========================================================================
 // dq kernel: 8 waves x 32 q rows; loops over 64-key KV tiles.
 // ===========================================================================
-template <int D>
+// VARLEN: packed [T, H(kv), D] layout, blockIdx.x = seg * H + h, segment
+// bounds from the device-side cu_seqlens (same contract as the fa2 forward's
+// varlen mode); LSE/DELTA are [H, lse_T].  A template flag, not a runtime
+// branch, so the dense / fused-qkv instantiation compiles exactly as before.
+template <int D, bool VARLEN>
 __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ DELTA,
     bf16* __restrict__ dQ, int B, int H, int Hkv, int S, int Skv,
     float scale, bool causal, FaStrides sq, FaStrides skv, FaStrides sdo,
-    FaStrides sdq) {
+    FaStrides sdq, const int* __restrict__ cu, int lse_T) {
   static_assert(D == 128);
   constexpr int KB = 64 * 256;     // 16 KiB per rm image
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -155,6 +159,15 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
   const int b = bh / H;
   const int hkv = h / (H / Hkv);
   const int q0 = blockIdx.y * 256;
+  int row0 = 0;
+  if constexpr (VARLEN) {
+    // b is the SEGMENT; block-uniform exit for empty segments and ragged
+    // tail tiles, before any load, clamp or barrier
+    row0 = cu[b];
+    S = cu[b + 1] - row0;
+    Skv = S;
+    if (q0 >= S) return;
+  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -163,15 +176,23 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
   const int hi = lane >> 5;
   const int g1 = (lane >> 4) & 1;
 
-  const bf16* Qb = Q + (int64_t)b * sq.bs + (int64_t)h * sq.hs;
-  const bf16* dOb = dO + (int64_t)b * sdo.bs + (int64_t)h * sdo.hs;
-  const bf16* Kb = K + (int64_t)b * skv.bs + (int64_t)hkv * skv.hs;
-  const bf16* Vb = V + (int64_t)b * skv.bs + (int64_t)hkv * skv.hs;
+  const bf16* Qb = Q + (VARLEN ? (int64_t)row0 * sq.rs : (int64_t)b * sq.bs)
+                 + (int64_t)h * sq.hs;
+  const bf16* dOb = dO
+      + (VARLEN ? (int64_t)row0 * sdo.rs : (int64_t)b * sdo.bs)
+      + (int64_t)h * sdo.hs;
+  const int64_t kb_off = VARLEN ? (int64_t)row0 * skv.rs
+                                : (int64_t)b * skv.bs;
+  const bf16* Kb = K + kb_off + (int64_t)hkv * skv.hs;
+  const bf16* Vb = V + kb_off + (int64_t)hkv * skv.hs;
 
   const int my_q = q0 + wid * 32 + iq;
   const int diag = Skv - S;
-  const float lse_q = LSE[(int64_t)bh * S + min(my_q, S - 1)];
-  const float del_q = DELTA[(int64_t)bh * S + min(my_q, S - 1)];
+  // LSE/DELTA rows: dense [B, H, S]; varlen [H, lse_T] at packed row
+  const int64_t stat0 = VARLEN ? ((int64_t)h * lse_T + row0)
+                               : ((int64_t)bh * S);
+  const float lse_q = LSE[stat0 + min(my_q, S - 1)];
+  const float del_q = DELTA[stat0 + min(my_q, S - 1)];
 
   // Q (scaled) and dO in registers
   bf16x8 qreg[8], doreg[8];
@@ -286,8 +307,9 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
 
   // ---- epilogue: dQ[my_q][d] = scale * dq^T[d][my_q] -------------------
   if (my_q < S) {
-    bf16* qrow = dQ + (int64_t)b * sdq.bs + (int64_t)h * sdq.hs
-               + (int64_t)my_q * sdq.rs;
+    bf16* qrow = dQ
+        + (VARLEN ? (int64_t)row0 * sdq.rs : (int64_t)b * sdq.bs)
+        + (int64_t)h * sdq.hs + (int64_t)my_q * sdq.rs;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
@@ -314,7 +336,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
 // ===========================================================================
 // dkv kernel: 8 waves x 32 keys (exclusive); loops over 32-q tiles.
 // ===========================================================================
-template <int D>
+template <int D, bool VARLEN>   // VARLEN: see fa2_bwd_dq_kernel
 // 132 KiB LDS -> occupancy 1 by LDS; see the fwd note on launch bounds
 __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -323,7 +345,8 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
     float* __restrict__ dK32, float* __restrict__ dV32,
     bf16* __restrict__ dK16, bf16* __restrict__ dV16,
     int B, int H, int Hkv, int S, int Skv, float scale, bool causal,
-    FaStrides sq, FaStrides skv, FaStrides sdo, FaStrides sdkv) {
+    FaStrides sq, FaStrides skv, FaStrides sdo, FaStrides sdkv,
+    const int* __restrict__ cu, int lse_T) {
   static_assert(D == 128);
   constexpr int QB = 32 * 256;     // 8 KiB per rm image
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -338,6 +361,14 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
   const int b = bh / H;
   const int hkv = h / (H / Hkv);
   const int kb0 = blockIdx.y * 256;
+  int row0 = 0;
+  if constexpr (VARLEN) {
+    // b is the SEGMENT; block-uniform exit before any load or barrier
+    row0 = cu[b];
+    S = cu[b + 1] - row0;
+    Skv = S;
+    if (kb0 >= Skv) return;
+  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -346,12 +377,19 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
   const int hi = lane >> 5;
   const int g1 = (lane >> 4) & 1;
 
-  const bf16* Qb = Q + (int64_t)b * sq.bs + (int64_t)h * sq.hs;
-  const bf16* dOb = dO + (int64_t)b * sdo.bs + (int64_t)h * sdo.hs;
-  const bf16* Kb = K + (int64_t)b * skv.bs + (int64_t)hkv * skv.hs;
-  const bf16* Vb = V + (int64_t)b * skv.bs + (int64_t)hkv * skv.hs;
-  const float* lse_b = LSE + (int64_t)bh * S;
-  const float* del_b = DELTA + (int64_t)bh * S;
+  const bf16* Qb = Q + (VARLEN ? (int64_t)row0 * sq.rs : (int64_t)b * sq.bs)
+                 + (int64_t)h * sq.hs;
+  const bf16* dOb = dO
+      + (VARLEN ? (int64_t)row0 * sdo.rs : (int64_t)b * sdo.bs)
+      + (int64_t)h * sdo.hs;
+  const int64_t kb_off = VARLEN ? (int64_t)row0 * skv.rs
+                                : (int64_t)b * skv.bs;
+  const bf16* Kb = K + kb_off + (int64_t)hkv * skv.hs;
+  const bf16* Vb = V + kb_off + (int64_t)hkv * skv.hs;
+  const int64_t stat0 = VARLEN ? ((int64_t)h * lse_T + row0)
+                               : ((int64_t)bh * S);
+  const float* lse_b = LSE + stat0;
+  const float* del_b = DELTA + stat0;
 
   const int my_key = kb0 + wid * 32 + iq;      // lane's exclusive key row
   const int diag = Skv - S;
@@ -527,14 +565,19 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
         float dkv_ = dk_acc[dt][r] * scale;
         float dvv_ = dv_acc[dt][r];
         if (gqa) {
-          // f32 accumulation buffers stay BHSD-contiguous
-          int64_t off32 = ((int64_t)(b * Hkv + hkv) * Skv + key) * D
-                        + 32 * dt + iq;
+          // f32 accumulation buffers: BHSD-contiguous (dense) or packed
+          // [T, Hkv, D] (varlen)
+          int64_t off32 =
+              (VARLEN ? ((int64_t)(row0 + key) * Hkv + hkv)
+                      : ((int64_t)(b * Hkv + hkv) * Skv + key)) * D
+              + 32 * dt + iq;
           atomicAdd(dK32 + off32, dkv_);
           atomicAdd(dV32 + off32, dvv_);
         } else {
-          int64_t off = (int64_t)b * sdkv.bs + (int64_t)hkv * sdkv.hs
-                      + (int64_t)key * sdkv.rs + 32 * dt + iq;
+          int64_t off =
+              (VARLEN ? (int64_t)row0 * sdkv.rs : (int64_t)b * sdkv.bs)
+              + (int64_t)hkv * sdkv.hs + (int64_t)key * sdkv.rs
+              + 32 * dt + iq;
           dK16[off] = (bf16)dkv_;
           dV16[off] = (bf16)dvv_;
         }
@@ -620,19 +663,21 @@ std::vector<torch::Tensor> fa2_bwd_core(
   {
     dim3 grid(B * H, (S + 255) / 256);
     size_t lds = 4 * (size_t)64 * 256;          // 64 KiB
-    hipLaunchKernelGGL(fa2_bwd_dq_kernel<128>, grid, dim3(THREADS), lds,
-                       stream, qp, kp, vp, doutp, lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), dqp,
-                       B, H, Hkv, S, Skv, scale, causal, sq, skv, sdo, sdq);
+    hipLaunchKernelGGL((fa2_bwd_dq_kernel<128, false>), grid, dim3(THREADS),
+                       lds, stream, qp, kp, vp, doutp,
+                       lse.data_ptr<float>(), delta.data_ptr<float>(), dqp,
+                       B, H, Hkv, S, Skv, scale, causal, sq, skv, sdo, sdq,
+                       (const int*)nullptr, 0);
   }
   {
     dim3 grid(B * H, (Skv + 255) / 256);
     size_t lds = 4 * (size_t)32 * 256 + 8 * 8192 + 8 * 4608;
-    hipLaunchKernelGGL(fa2_bwd_dkv_kernel<128>, grid, dim3(THREADS), lds,
-                       stream, qp, kp, vp, doutp, lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), dk32p, dv32p, dk16p, dv16p,
+    hipLaunchKernelGGL((fa2_bwd_dkv_kernel<128, false>), grid,
+                       dim3(THREADS), lds, stream, qp, kp, vp, doutp,
+                       lse.data_ptr<float>(), delta.data_ptr<float>(),
+                       dk32p, dv32p, dk16p, dv16p,
                        B, H, Hkv, S, Skv, scale, causal, sq, skv, sdo,
-                       sdkv);
+                       sdkv, (const int*)nullptr, 0);
   }
   return {};
 }
@@ -668,6 +713,94 @@ std::vector<torch::Tensor> fa2_bwd_launch(
   if (gqa) {
     return {dq, dk32.to(k.scalar_type()), dv32.to(v.scalar_type())};
   }
+  return {dq, dk16, dv16};
+}
+
+// Packed-varlen backward (analogue of flash_attn_varlen_fwd): delta + dq +
+// dkv, ONE launch each over all ragged segments; dout/q/k/v/out [T, H(kv), D]
+// packed, lse [H, T] fp32, cu int32 [nseg+1] on DEVICE — no host sync.
+// max_seqlen only sizes the grid and must be >= the longest segment.
+// Rows outside every segment (t >= cu[-1]) come back zero.
+std::vector<torch::Tensor> flash_attn_varlen_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse, torch::Tensor cu,
+    int64_t max_seqlen, bool causal, double scale) {
+  TORCH_CHECK(q.dim() == 3 && q.is_contiguous() && k.is_contiguous() &&
+              v.is_contiguous(), "varlen: q/k/v [T, H, D] contiguous");
+  TORCH_CHECK(dout.is_contiguous() && out.is_contiguous() &&
+              dout.sizes() == q.sizes() && out.sizes() == q.sizes(),
+              "varlen: dout/out [T, H, D] contiguous");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 &&
+              k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16 &&
+              dout.scalar_type() == at::kBFloat16 &&
+              out.scalar_type() == at::kBFloat16, "varlen: bf16 only");
+  TORCH_CHECK(cu.scalar_type() == at::kInt && cu.is_cuda() &&
+              cu.is_contiguous(), "varlen: cu int32 on device");
+  const int T = q.size(0), H = q.size(1), D = q.size(2);
+  const int Hkv = k.size(1);
+  TORCH_CHECK(D == 128, "fa2 varlen: D=128 only");
+  TORCH_CHECK(k.dim() == 3 && k.size(0) == T && k.size(2) == D &&
+              v.sizes() == k.sizes() && Hkv > 0 && H % Hkv == 0,
+              "varlen: k/v [T, Hkv, D]");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.dim() == 2 && lse.size(0) == H && lse.size(1) == T,
+              "varlen: lse [H, T] fp32");
+  const int nseg = cu.numel() - 1;
+  const bool gqa = (H != Hkv);
+  // zero-filled: rows past cu[-1] belong to no segment and no block
+  auto dq = torch::zeros_like(q);
+  torch::Tensor dk16, dv16, dk32, dv32;
+  if (gqa) {
+    dk32 = torch::zeros_like(k, k.options().dtype(at::kFloat));
+    dv32 = torch::zeros_like(v, v.options().dtype(at::kFloat));
+  } else {
+    dk16 = torch::zeros_like(k);
+    dv16 = torch::zeros_like(v);
+  }
+  if (nseg <= 0 || T == 0 || max_seqlen <= 0) {
+    if (gqa) return {dq, dk32.to(k.scalar_type()), dv32.to(v.scalar_type())};
+    return {dq, dk16, dv16};
+  }
+  FaStrides sq{0, (long long)D, (long long)H * D};
+  FaStrides skv{0, (long long)D, (long long)Hkv * D};
+  auto stream = hetu_current_stream();
+  auto delta = torch::empty({H, (int64_t)T}, lse.options());
+  {
+    // [1, H, T] from packed dO/O: the dense kernel with B=1, S=T
+    int64_t rows = (int64_t)H * T;
+    int grid = (int)std::min<int64_t>((rows * 4 + 255) / 256, 16384);
+    hipLaunchKernelGGL(fa2_delta_kernel, dim3(grid), dim3(256), 0, stream,
+                       (const bf16*)dout.data_ptr(),
+                       (const bf16*)out.data_ptr(), delta.data_ptr<float>(),
+                       rows, D, H, T, sq);
+  }
+  dim3 grid(nseg * H, ((int)max_seqlen + 255) / 256);
+  {
+    size_t lds = 4 * (size_t)64 * 256;          // 64 KiB
+    hipLaunchKernelGGL((fa2_bwd_dq_kernel<128, true>), grid, dim3(THREADS),
+                       lds, stream, (const bf16*)q.data_ptr(),
+                       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
+                       (const bf16*)dout.data_ptr(), lse.data_ptr<float>(),
+                       delta.data_ptr<float>(), (bf16*)dq.data_ptr(),
+                       nseg, H, Hkv, 0, 0, (float)scale, causal, sq, skv, sq,
+                       sq, cu.data_ptr<int>(), T);
+  }
+  {
+    size_t lds = 4 * (size_t)32 * 256 + 8 * 8192 + 8 * 4608;
+    hipLaunchKernelGGL((fa2_bwd_dkv_kernel<128, true>), grid, dim3(THREADS),
+                       lds, stream, (const bf16*)q.data_ptr(),
+                       (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
+                       (const bf16*)dout.data_ptr(), lse.data_ptr<float>(),
+                       delta.data_ptr<float>(),
+                       gqa ? dk32.data_ptr<float>() : nullptr,
+                       gqa ? dv32.data_ptr<float>() : nullptr,
+                       gqa ? nullptr : (bf16*)dk16.data_ptr(),
+                       gqa ? nullptr : (bf16*)dv16.data_ptr(),
+                       nseg, H, Hkv, 0, 0, (float)scale, causal, sq, skv, sq,
+                       skv, cu.data_ptr<int>(), T);
+  }
+  if (gqa) return {dq, dk32.to(k.scalar_type()), dv32.to(v.scalar_type())};
   return {dq, dk16, dv16};
 }
 

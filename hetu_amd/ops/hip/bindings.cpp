@@ -128,6 +128,11 @@ void rope_qk_inplace(torch::Tensor qkv, torch::Tensor cs, torch::Tensor sn,
 std::vector<torch::Tensor> flash_attn_varlen_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor cu,
     int64_t max_seqlen, bool causal, double scale);
+// attention_bwd_v2.hip
+std::vector<torch::Tensor> flash_attn_varlen_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor out, torch::Tensor lse, torch::Tensor cu,
+    int64_t max_seqlen, bool causal, double scale);
 std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
                                              torch::Tensor k,
                                              torch::Tensor v, bool causal,
@@ -189,6 +194,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd", &flash_attn_bwd);
   m.def("flash_attn_fwd_qkv", &flash_attn_fwd_qkv);
   m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd);
+  m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
   m.def("flash_attn_bwd_qkv", &flash_attn_bwd_qkv);
   m.def("rope_qk_inplace", &rope_qk_inplace);
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3);
