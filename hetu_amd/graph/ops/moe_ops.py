@@ -14,6 +14,10 @@ C = per-(source rank, expert) capacity):
     meta:      pos [E, C] int64 (token index per slot, -1 pad) — kept as a
                graph tensor so combine/grads replay the routing
   combine: expert_out [El, P*C, h], combine_w, pos -> y [N, h]
+
+Routing and the row movement on either side of the a2a go through the
+ops.functional moe_* entry points (moe.hip kernels on a GPU, the torch
+composition on CPU).
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import os
 
 import torch
 
+from ...ops import functional as F
 from ...parallel.dstates import DistributedStates
 from ..op import OpInterface
 from ..tensor import TensorMeta
@@ -45,40 +50,6 @@ def _a2a(comm, ranks, x):
     if ns > 1:
         return hierarchical_alltoall(comm, ranks, x, ns)
     return alltoall(comm, ranks, x)
-
-
-def _route(probs: torch.Tensor, E: int, C: int, K: int):
-    """Greedy capacity routing.  Returns pos [E, C] int64 (-1 pad),
-    combine scatter info: slot_of [N, K] int64 (flat index into E*C, -1 if
-    dropped), topk idx [N, K], weights [N, K].
-
-    Fully static shapes: no nonzero/boolean-mask gathers, so the routing
-    is hipGraph-capturable and never syncs the host (dropped tokens
-    scatter into a sacrificial slot E*C instead)."""
-    N = probs.shape[0]
-    dev = probs.device
-    w, idx = probs.topk(K, dim=-1)                      # [N, K]
-    # pos with one extra dummy slot at index E*C for dropped tokens
-    pos_fl = torch.full((E * C + 1,), -1, dtype=torch.int64, device=dev)
-    slot_of = torch.full((N, K), -1, dtype=torch.int64, device=dev)
-    toks = torch.arange(N, dtype=torch.int64, device=dev)
-    base = torch.zeros(E, dtype=torch.int64, device=dev)
-    for k in range(K):
-        e = idx[:, k]                                   # [N]
-        onehot = torch.nn.functional.one_hot(e, E)      # [N, E]
-        order = onehot.cumsum(0) * onehot               # 1-based rank
-        q = (order.gather(1, e.unsqueeze(1)).squeeze(1) - 1) + base[e]
-        keep = q < C
-        flat = torch.where(keep, e * C + q,
-                           torch.full_like(q, E * C))  # dummy if dropped
-        pos_fl.scatter_(0, flat, toks)
-        slot_of[:, k] = torch.where(keep, flat,
-                                    torch.full_like(flat, -1))
-        # recount filled slots per expert (robust to same-slot rewrites)
-        base = (pos_fl[:E * C].reshape(E, C) >= 0).sum(-1)
-    pos = pos_fl[:E * C].reshape(E, C)
-    wk = torch.where(slot_of >= 0, w, torch.zeros_like(w))
-    return pos, slot_of, idx, wk
 
 
 class MoEDispatchOp(OpInterface):
@@ -115,10 +86,8 @@ class MoEDispatchOp(OpInterface):
         ranks = _ep_ranks(op, ctx)
         P = len(ranks)
         El = E // P
-        pos, slot_of, idx, wk = _route(probs.float(), E, C, K)
-        # static-shape gather: dropped slots read token 0 and are masked
-        pf = pos.view(-1)
-        send = x[pf.clamp(min=0)] * (pf >= 0).unsqueeze(-1).to(x.dtype)
+        pos, slot_of, idx, wk = F.moe_route(probs, C, K)
+        send = F.moe_dispatch_rows(x, pos)
         if P > 1:
             # [E*C, h] = [P, El*C, h] blocks by destination rank
             recv = _a2a(ctx.comm, ranks, send)
@@ -165,17 +134,11 @@ class MoEDispatchGradOp(OpInterface):
             gsend = _a2a(ctx.comm, ranks, back)
         else:
             gsend = g_exp.reshape(E * C, -1)
-        dx = torch.zeros_like(x)
-        pf = pos.view(-1)
-        dx.index_add_(0, pf.clamp(min=0),
-                      (gsend * (pf >= 0).unsqueeze(-1)).to(x.dtype))
-        # dprobs: combine_w = probs.gather(topk) masked -> scatter g_w
-        dprobs = torch.zeros_like(probs)
+        dx = F.moe_dispatch_rows_bwd(gsend.to(x.dtype), pos, slot_of)
         if g_w is not None:
-            wmask = (slot_of >= 0).to(probs.dtype)
-            # idx recomputed from probs (same topk order)
-            _, idx = probs.float().topk(K, dim=-1)
-            dprobs.scatter_(1, idx, (g_w.to(probs.dtype) * wmask))
+            dprobs = F.moe_gate_bwd(g_w, slot_of, probs, C)
+        else:
+            dprobs = torch.zeros_like(probs)
         return [dx, dprobs]
 
 
@@ -211,14 +174,7 @@ class MoECombineOp(OpInterface):
         P = len(ranks)
         El = E // P
         recv = self._gather_back(eo, pos, ranks, ctx, E, C, P, El)
-        N = wk.shape[0]
-        y = eo.new_zeros(N, eo.shape[-1])
-        for k in range(K):
-            sl = slot_of[:, k]
-            rows = recv[sl.clamp(min=0)]
-            # wk is already 0 for dropped slots (masked at routing)
-            y += rows * wk[:, k].unsqueeze(-1).to(rows.dtype)
-        return [y]
+        return [F.moe_combine_rows(recv, wk, slot_of)]
 
     def gradient(self, op, g):
         gr = _g(op.outputs[0])
@@ -245,23 +201,8 @@ class MoECombineGradOp(OpInterface):
         ranks = _ep_ranks(op, ctx)
         P = len(ranks)
         El = E // P
-        # d_recv [E*C, h]: rows scattered from gy * w (slot E*C is the
-        # sacrificial target for dropped entries — static shapes)
-        h = gy.shape[-1]
-        d_fl = gy.new_zeros(E * C + 1, h)
-        for k in range(K):
-            sl = slot_of[:, k]
-            tgt = torch.where(sl >= 0, sl, torch.full_like(sl, E * C))
-            d_fl.scatter_(0, tgt.unsqueeze(-1).expand(-1, h),
-                          gy * wk[:, k].unsqueeze(-1).to(gy.dtype))
-        d_recv = d_fl[:E * C]
-        # d_combine_w: dot(gy[token], recv[slot]); 0 where dropped
         recv = MoECombineOp._gather_back(eo, pos, ranks, ctx, E, C, P, El)
-        dwk = torch.zeros_like(wk)
-        for k in range(K):
-            sl = slot_of[:, k]
-            dot = (gy.float() * recv[sl.clamp(min=0)].float()).sum(-1)
-            dwk[:, k] = dot * (sl >= 0).to(dot.dtype)
+        d_recv, dwk = F.moe_combine_rows_bwd(gy, recv, wk, pos, slot_of)
         # forward a2a of d_recv to expert layout
         if P > 1:
             recv2 = _a2a(ctx.comm, ranks, d_recv)

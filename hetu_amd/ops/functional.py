@@ -69,7 +69,7 @@ def _gpu(*ts) -> bool:
 # Debug bisect switch: HETU_AMD_TORCH_FALLBACK="fa,ln,adam,..." routes the
 # named kernel families to the plain-torch reference implementations even
 # on GPU (they are device-agnostic).  Families: fa, qkvfa, ln, rms, gelu,
-# silu, swiglu, adam, ce, vce, embed, softmax, rope, dropout.
+# silu, swiglu, adam, ce, vce, embed, softmax, rope, dropout, moe.
 _TORCH_FB = frozenset(
     s for s in os.environ.get("HETU_AMD_TORCH_FALLBACK", "").split(",") if s)
 
@@ -860,3 +860,172 @@ def dgelu_bgrad(dy2d, w, aux):
     da = torch.matmul(dy2d, w.to(dy2d.dtype))
     dh = gelu_bwd(da, aux)
     return dh, colsum(dh).to(dh.dtype)
+
+
+# ---------------------------------------------------------------------------
+# MoE routing / layout (moe.hip; reference TopKIdx.cu, LayoutTransform.cu,
+# ReverseLayoutTransform).  N tokens, E experts, C slots per expert, K
+# choices per token:
+#   pos     [E, C] int64   token index held by each slot, -1 if empty
+#   slot_of [N, K] int64   flat slot e*C + q of choice k, -1 if dropped
+#   wk      [N, K] fp32    gate weight of choice k, 0 if dropped
+# Routing policy: rounds k = 0..K-1 in order; within a round tokens queue at
+# their expert in increasing token index, behind the slots earlier rounds
+# filled; a choice is kept iff its queue position is < C.  The HIP top-k
+# breaks ties towards the lower expert index (torch.topk leaves tie order
+# unspecified).  The torch branches are the composition the graph ops used
+# before the kernels existed; they serve CPU, HETU_AMD_TORCH_FALLBACK=moe
+# and K / E beyond the kernel limits.
+# ---------------------------------------------------------------------------
+
+MOE_MAX_K = 8
+MOE_MAX_E = 2048
+
+
+def _moe_hip(K: int, E: int, *ts) -> bool:
+    return (_use_hip("moe", *ts) and 1 <= K <= MOE_MAX_K and K <= E
+            and E <= MOE_MAX_E)
+
+
+def _moe_route_torch(probs: torch.Tensor, E: int, C: int, K: int):
+    """Greedy capacity routing.  Returns pos [E, C] int64 (-1 pad),
+    combine scatter info: slot_of [N, K] int64 (flat index into E*C, -1 if
+    dropped), topk idx [N, K], weights [N, K].
+
+    Fully static shapes: no nonzero/boolean-mask gathers, so the routing
+    is hipGraph-capturable and never syncs the host (dropped tokens
+    scatter into a sacrificial slot E*C instead)."""
+    N = probs.shape[0]
+    dev = probs.device
+    w, idx = probs.topk(K, dim=-1)                      # [N, K]
+    # pos with one extra dummy slot at index E*C for dropped tokens
+    pos_fl = torch.full((E * C + 1,), -1, dtype=torch.int64, device=dev)
+    slot_of = torch.full((N, K), -1, dtype=torch.int64, device=dev)
+    toks = torch.arange(N, dtype=torch.int64, device=dev)
+    base = torch.zeros(E, dtype=torch.int64, device=dev)
+    for k in range(K):
+        e = idx[:, k]                                   # [N]
+        onehot = torch.nn.functional.one_hot(e, E)      # [N, E]
+        order = onehot.cumsum(0) * onehot               # 1-based rank
+        q = (order.gather(1, e.unsqueeze(1)).squeeze(1) - 1) + base[e]
+        keep = q < C
+        flat = torch.where(keep, e * C + q,
+                           torch.full_like(q, E * C))  # dummy if dropped
+        pos_fl.scatter_(0, flat, toks)
+        slot_of[:, k] = torch.where(keep, flat,
+                                    torch.full_like(flat, -1))
+        # recount filled slots per expert (robust to same-slot rewrites)
+        base = (pos_fl[:E * C].reshape(E, C) >= 0).sum(-1)
+    pos = pos_fl[:E * C].reshape(E, C)
+    wk = torch.where(slot_of >= 0, w, torch.zeros_like(w))
+    return pos, slot_of, idx, wk
+
+
+def moe_route(probs: torch.Tensor, C: int, K: int):
+    """probs [N, E] -> (pos [E, C], slot_of [N, K], idx [N, K] int64,
+    wk [N, K] fp32).  Values compare in fp32."""
+    E = probs.shape[1]
+    if _moe_hip(K, E, probs):
+        idx, w = ext().moe_topk(probs.contiguous(), K)
+        pos, slot_of, wk = ext().moe_assign_slots(idx, w, E, C)
+        return pos, slot_of, idx, wk
+    return _moe_route_torch(probs.float(), E, C, K)
+
+
+def moe_dispatch_rows(x: torch.Tensor, pos: torch.Tensor, out=None):
+    """x [N, h], pos [E, C] -> send [E*C, h]: row s is x[pos[s]], zeros
+    for an empty slot.  `out` (HIP path only) receives the rows."""
+    if _use_hip("moe", x):
+        return ext().moe_dispatch_rows(x.contiguous(), pos.contiguous(), out)
+    # static-shape gather: dropped slots read token 0 and are masked
+    pf = pos.view(-1)
+    send = x[pf.clamp(min=0)] * (pf >= 0).unsqueeze(-1).to(x.dtype)
+    if out is not None:
+        out.copy_(send)
+        return out
+    return send
+
+
+def moe_dispatch_rows_bwd(gsend: torch.Tensor, pos: torch.Tensor,
+                          slot_of: torch.Tensor):
+    """gsend [E*C, h] -> dx [N, h]: dx[t] = sum of the gsend rows of t's
+    kept slots (fp32 accumulation, one rounding on the HIP path)."""
+    N, K = slot_of.shape
+    if _use_hip("moe", gsend) and 1 <= K <= MOE_MAX_K:
+        return ext().moe_dispatch_rows_bwd(gsend.contiguous(),
+                                           slot_of.contiguous())
+    dx = gsend.new_zeros(N, gsend.shape[-1])
+    pf = pos.view(-1)
+    dx.index_add_(0, pf.clamp(min=0),
+                  (gsend * (pf >= 0).unsqueeze(-1)).to(dx.dtype))
+    return dx
+
+
+def moe_gate_bwd(g_w: torch.Tensor, slot_of: torch.Tensor,
+                 probs: torch.Tensor, C: int):
+    """g_w [N, K] -> dprobs [N, E] (dtype of probs): g_w lands on the
+    expert of every kept choice, zero elsewhere."""
+    K = slot_of.shape[1]
+    if _moe_hip(K, probs.shape[1], probs):
+        return ext().moe_gate_bwd(g_w.float().contiguous(),
+                                  slot_of.contiguous(), probs, C)
+    # dprobs: combine_w = probs.gather(topk) masked -> scatter g_w
+    dprobs = torch.zeros_like(probs)
+    wmask = (slot_of >= 0).to(probs.dtype)
+    # idx recomputed from probs (same topk order)
+    _, idx = probs.float().topk(K, dim=-1)
+    dprobs.scatter_(1, idx, (g_w.to(probs.dtype) * wmask))
+    return dprobs
+
+
+def moe_combine_rows(recv: torch.Tensor, wk: torch.Tensor,
+                     slot_of: torch.Tensor):
+    """recv [E*C, h] -> y [N, h]: y[t] = sum_k wk[t,k] * recv[slot_of[t,k]]
+    over kept k."""
+    N, K = slot_of.shape
+    if _use_hip("moe", recv) and 1 <= K <= MOE_MAX_K:
+        return ext().moe_combine_rows(recv.contiguous(),
+                                      wk.float().contiguous(),
+                                      slot_of.contiguous())
+    y = recv.new_zeros(N, recv.shape[-1])
+    for k in range(K):
+        sl = slot_of[:, k]
+        rows = recv[sl.clamp(min=0)]
+        # wk is already 0 for dropped slots (masked at routing)
+        y += rows * wk[:, k].unsqueeze(-1).to(rows.dtype)
+    return y
+
+
+def moe_combine_rows_bwd(gy: torch.Tensor, recv: torch.Tensor,
+                         wk: torch.Tensor, pos: torch.Tensor,
+                         slot_of: torch.Tensor, out=None):
+    """-> (d_recv [E*C, h], dwk [N, K] fp32): d_recv[s] = gy[t] * wk[t,k]
+    for the (t, k) holding slot s, zeros for an empty slot;
+    dwk[t,k] = <gy[t], recv[slot_of[t,k]]> in fp32, 0 if dropped.  `out`
+    (HIP path only) receives d_recv."""
+    N, K = slot_of.shape
+    if _use_hip("moe", gy) and 1 <= K <= MOE_MAX_K:
+        return tuple(ext().moe_combine_rows_bwd(
+            gy.contiguous(), recv.contiguous(), wk.float().contiguous(),
+            pos.contiguous(), slot_of.contiguous(), out))
+    # d_recv [E*C, h]: rows scattered from gy * w (slot E*C is the
+    # sacrificial target for dropped entries — static shapes)
+    h = gy.shape[-1]
+    EC = pos.numel()
+    d_fl = gy.new_zeros(EC + 1, h)
+    for k in range(K):
+        sl = slot_of[:, k]
+        tgt = torch.where(sl >= 0, sl, torch.full_like(sl, EC))
+        d_fl.scatter_(0, tgt.unsqueeze(-1).expand(-1, h),
+                      gy * wk[:, k].unsqueeze(-1).to(gy.dtype))
+    d_recv = d_fl[:EC]
+    # d_combine_w: dot(gy[token], recv[slot]); 0 where dropped
+    dwk = torch.zeros_like(wk)
+    for k in range(K):
+        sl = slot_of[:, k]
+        dot = (gy.float() * recv[sl.clamp(min=0)].float()).sum(-1)
+        dwk[:, k] = dot * (sl >= 0).to(dot.dtype)
+    if out is not None:
+        out.copy_(d_recv)
+        d_recv = out
+    return d_recv, dwk

@@ -144,6 +144,23 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
                                              torch::Tensor out,
                                              torch::Tensor lse,
                                              bool causal, double scale);
+// moe.hip
+std::vector<torch::Tensor> moe_topk(torch::Tensor probs, int64_t K);
+std::vector<torch::Tensor> moe_assign_slots(torch::Tensor idx,
+                                            torch::Tensor w, int64_t E,
+                                            int64_t C);
+torch::Tensor moe_dispatch_rows(torch::Tensor x, torch::Tensor pos,
+                                c10::optional<torch::Tensor> out);
+torch::Tensor moe_dispatch_rows_bwd(torch::Tensor gsend,
+                                    torch::Tensor slot_of);
+torch::Tensor moe_gate_bwd(torch::Tensor g_w, torch::Tensor slot_of,
+                           torch::Tensor probs, int64_t C);
+torch::Tensor moe_combine_rows(torch::Tensor recv, torch::Tensor wk,
+                               torch::Tensor slot_of);
+std::vector<torch::Tensor> moe_combine_rows_bwd(
+    torch::Tensor gy, torch::Tensor recv, torch::Tensor wk,
+    torch::Tensor pos, torch::Tensor slot_of,
+    c10::optional<torch::Tensor> out);
 
 // embed_cache.cpp
 void register_embed_cache(pybind11::module& m);
@@ -199,4 +216,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_qk_inplace", &rope_qk_inplace);
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3);
   m.def("flash_attn_bwd_v3", &flash_attn_bwd_v3);
+  m.def("moe_topk", &moe_topk);
+  m.def("moe_assign_slots", &moe_assign_slots);
+  m.def("moe_dispatch_rows", &moe_dispatch_rows, pybind11::arg("x"),
+        pybind11::arg("pos"), pybind11::arg("out") = pybind11::none());
+  m.def("moe_dispatch_rows_bwd", &moe_dispatch_rows_bwd);
+  m.def("moe_gate_bwd", &moe_gate_bwd);
+  m.def("moe_combine_rows", &moe_combine_rows);
+  m.def("moe_combine_rows_bwd", &moe_combine_rows_bwd, pybind11::arg("gy"),
+        pybind11::arg("recv"), pybind11::arg("wk"), pybind11::arg("pos"),
+        pybind11::arg("slot_of"), pybind11::arg("out") = pybind11::none());
 }

@@ -32,6 +32,7 @@ SOURCES = [
     "attention_bwd_v3.hip",
     "attention_bwd_v2.hip",
     "quant.hip",
+    "moe.hip",
     "ltgemm.cpp",
     "galvatron_dp.cpp",
     "embed_cache.cpp",
