@@ -78,6 +78,11 @@ def _use_hip(family: str, *ts) -> bool:
     return _gpu(*ts) and family not in _TORCH_FB
 
 
+# Debug bisect switch: HETU_AMD_FA1=1 routes dense flash attention to the
+# v1 kernels (impl=1); otherwise the extension picks the variant by shape.
+_FA_IMPL = 1 if os.environ.get("HETU_AMD_FA1", "")[:1] == "1" else 0
+
+
 # ---------------------------------------------------------------------------
 # RMSNorm (fused fwd/bwd; reference RMSNorm.cu — block per row)
 # ---------------------------------------------------------------------------
@@ -473,7 +478,7 @@ def flash_attn_fwd(q, k, v, causal: bool, scale: Optional[float] = None):
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _use_hip("fa", q):
         return ext().flash_attn_fwd(q.contiguous(), k.contiguous(),
-                                    v.contiguous(), causal, scale)
+                                    v.contiguous(), causal, scale, _FA_IMPL)
     return _attn_ref_fwd(q, k, v, causal, scale)
 
 
@@ -482,21 +487,10 @@ def flash_attn_bwd(dout, q, k, v, out, lse, causal: bool,
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _use_hip("fa", q):
-        e = ext()
-        if q.shape[1] == k.shape[1] and q.shape[-1] == 128 \
-                and hasattr(e, "flash_attn_bwd_v3") \
-                and os.environ.get("HETU_AMD_FA_V3", "1") == "1":
-            # v3 bwd: 3-deep walking-pointer staging rings + counted
-            # vmcnt (bit-exact vs v2, ~6% faster on the causal bwd at
-            # S=2048 — gpurun_out/r2_fa_bench.log); non-GQA BHSD only
-            return e.flash_attn_bwd_v3(dout.contiguous(), q.contiguous(),
-                                       k.contiguous(), v.contiguous(),
-                                       out.contiguous(), lse.contiguous(),
-                                       causal, scale)
-        return e.flash_attn_bwd(dout.contiguous(), q.contiguous(),
-                                k.contiguous(), v.contiguous(),
-                                out.contiguous(), lse.contiguous(),
-                                causal, scale)
+        return ext().flash_attn_bwd(dout.contiguous(), q.contiguous(),
+                                    k.contiguous(), v.contiguous(),
+                                    out.contiguous(), lse.contiguous(),
+                                    causal, scale, _FA_IMPL)
     return _attn_ref_bwd(dout, q, k, v, out, lse, causal, scale)
 
 

@@ -18,11 +18,10 @@
 //    bank conflict (guide §6 Guideline 4).
 #include <torch/extension.h>
 #include "ext_stream.h"
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int BM = 64;     // query-tile rows
@@ -50,9 +49,7 @@ DEV void stage_rm(const bf16* __restrict__ gsrc, int64_t row_stride_elts,
     // 0 * NaN = NaN inside the MFMAs even for masked entries
     const bf16* src = gsrc + (int64_t)min(row, max_row) * row_stride_elts
                     + sc / 2;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)src,
-        (__attribute__((address_space(3))) void*)(lds + lin), 16, 0, 0);
+    fa_glds16(src, lds + lin);
   }
 }
 
@@ -541,37 +538,43 @@ __global__ __launch_bounds__(THREADS) void fa_bwd_kernel(
   }
 }
 
-}  // namespace
+// The one place a kernel generation is chosen.  impl 0 picks by shape:
+// v1 (this file) unless D == 128; at D == 128 the backward of non-GQA
+// attention takes v3 and everything else v2.  impl 1/2/3 demands exactly
+// that generation (tests, A/B timing, the HETU_AMD_FA1 bisect switch) and
+// is an error where the generation does not cover the shape.
+int fa_pick_impl(int64_t impl, bool bwd, int D, bool gqa) {
+  TORCH_CHECK(D == 64 || D == 128, "flash_attn: head dim 64/128");
+  if (impl == 0) return D != 128 ? 1 : (bwd && !gqa) ? 3 : 2;
+  TORCH_CHECK(impl == 1 || (impl == 2 && D == 128) ||
+              (impl == 3 && bwd && D == 128 && !gqa),
+              "flash_attn: impl=", impl, " does not support ",
+              bwd ? "backward" : "forward", " D=", D, gqa ? " GQA" : "");
+  return (int)impl;
+}
 
-bool fa2_fwd_supported(int D, int S);
-void fa2_fwd_launch(const void* q, const void* k, const void* v, void* o,
-                    float* lse, int B, int H, int Hkv, int S, int Skv,
-                    float scale, bool causal, hipStream_t stream,
-                    FaStrides sq, FaStrides skv, FaStrides so);
+}  // namespace
 
 std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
                                           torch::Tensor v, bool causal,
-                                          double scale) {
+                                          double scale, int64_t impl) {
   TORCH_CHECK(q.dim() == 4, "q must be [B,H,S,D]");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "flash_attn: bf16 only");
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int Hkv = k.size(1), Skv = k.size(2);
-  TORCH_CHECK(D == 64 || D == 128, "flash_attn: head dim 64/128");
   TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+  const int variant = fa_pick_impl(impl, false, D, H != Hkv);
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, S}, q.options().dtype(at::kFloat));
   auto stream = hetu_current_stream();
-  static const bool force_v1 = [] {
-    const char* e = getenv("HETU_AMD_FA1");
-    return e && e[0] == '1';
-  }();
-  if (!force_v1 && fa2_fwd_supported(D, S)) {
+  if (variant == 2) {
     FaStrides sq{(long long)H * S * D, (long long)S * D, (long long)D};
     FaStrides skv{(long long)Hkv * Skv * D, (long long)Skv * D,
                   (long long)D};
-    fa2_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+    fa2_fwd_launch((const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
+                   (const bf16*)v.data_ptr(), (bf16*)o.data_ptr(),
                    lse.data_ptr<float>(), B, H, Hkv, S, Skv, (float)scale,
-                   causal, stream, sq, skv, sq);
+                   causal, sq, skv, sq, nullptr, 0, stream);
     return {o, lse};
   }
   dim3 grid((S + BM - 1) / BM, B * H);
@@ -592,25 +595,18 @@ std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
   return {o, lse};
 }
 
-bool fa2_bwd_supported(int D, int S);
-std::vector<torch::Tensor> fa2_bwd_launch(
-    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
-    torch::Tensor out, torch::Tensor lse, bool causal, double scale);
-
 std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout,
                                           torch::Tensor q, torch::Tensor k,
                                           torch::Tensor v, torch::Tensor out,
                                           torch::Tensor lse, bool causal,
-                                          double scale) {
+                                          double scale, int64_t impl) {
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int Hkv = k.size(1), Skv = k.size(2);
-  static const bool bwd_force_v1 = [] {
-    const char* e = getenv("HETU_AMD_FA1");
-    return e && e[0] == '1';
-  }();
-  if (!bwd_force_v1 && fa2_bwd_supported(D, S)) {
+  const int variant = fa_pick_impl(impl, true, D, H != Hkv);
+  if (variant == 3)
+    return fa3_bwd_launch(dout, q, k, v, out, lse, causal, scale);
+  if (variant == 2)
     return fa2_bwd_launch(dout, q, k, v, out, lse, causal, scale);
-  }
   auto stream = hetu_current_stream();
   auto delta = torch::empty({B, H, S}, q.options().dtype(at::kFloat));
   {

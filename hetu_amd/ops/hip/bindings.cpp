@@ -104,46 +104,35 @@ torch::Tensor dequantize_blockwise(torch::Tensor q, torch::Tensor absmax,
 std::pair<double, std::vector<int64_t>> galvatron_dp(
     std::vector<double> times, std::vector<double> mems, int64_t L,
     int64_t S, double cap, int64_t buckets);
-// attention.hip
+// attention.hip: the dense [B,H,S,D] entries and the variant choice
+// (impl 0 = by shape, 1/2/3 = exactly that kernel generation)
 std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
                                           torch::Tensor v, bool causal,
-                                          double scale);
+                                          double scale, int64_t impl);
 std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout,
                                           torch::Tensor q, torch::Tensor k,
                                           torch::Tensor v, torch::Tensor out,
                                           torch::Tensor lse, bool causal,
-                                          double scale);
-// fused-qkv fast path (attention_v2 / attention_bwd_v2)
+                                          double scale, int64_t impl);
+// attention_v2.hip: fused-qkv and packed-varlen forward
 std::vector<torch::Tensor> flash_attn_fwd_qkv(torch::Tensor qkv, int64_t H,
                                               int64_t Hkv, int64_t D,
                                               bool causal, double scale);
+std::vector<torch::Tensor> flash_attn_varlen_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor cu,
+    int64_t max_seqlen, bool causal, double scale);
+// attention_bwd_v2.hip: fused-qkv and packed-varlen backward
 torch::Tensor flash_attn_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                                  torch::Tensor out, torch::Tensor lse,
                                  int64_t H, int64_t Hkv, int64_t D,
                                  bool causal, double scale);
-// rope.hip
-void rope_qk_inplace(torch::Tensor qkv, torch::Tensor cs, torch::Tensor sn,
-                     int64_t n_rot, int64_t D, int64_t sign);
-// attention_v3.hip (experimental round-2 candidate)
-std::vector<torch::Tensor> flash_attn_varlen_fwd(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor cu,
-    int64_t max_seqlen, bool causal, double scale);
-// attention_bwd_v2.hip
 std::vector<torch::Tensor> flash_attn_varlen_bwd(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor out, torch::Tensor lse, torch::Tensor cu,
     int64_t max_seqlen, bool causal, double scale);
-std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q,
-                                             torch::Tensor k,
-                                             torch::Tensor v, bool causal,
-                                             double scale);
-std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
-                                             torch::Tensor q,
-                                             torch::Tensor k,
-                                             torch::Tensor v,
-                                             torch::Tensor out,
-                                             torch::Tensor lse,
-                                             bool causal, double scale);
+// rope.hip
+void rope_qk_inplace(torch::Tensor qkv, torch::Tensor cs, torch::Tensor sn,
+                     int64_t n_rot, int64_t D, int64_t sign);
 // moe.hip
 std::vector<torch::Tensor> moe_topk(torch::Tensor probs, int64_t K);
 std::vector<torch::Tensor> moe_assign_slots(torch::Tensor idx,
@@ -207,15 +196,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quantize_blockwise", &quantize_blockwise);
   m.def("dequantize_blockwise", &dequantize_blockwise);
   m.def("galvatron_dp", &galvatron_dp);
-  m.def("flash_attn_fwd", &flash_attn_fwd);
-  m.def("flash_attn_bwd", &flash_attn_bwd);
+  m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("causal"), py::arg("scale"),
+        py::arg("impl") = 0);
+  m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("dout"), py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"),
+        py::arg("causal"), py::arg("scale"), py::arg("impl") = 0);
   m.def("flash_attn_fwd_qkv", &flash_attn_fwd_qkv);
   m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd);
   m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
   m.def("flash_attn_bwd_qkv", &flash_attn_bwd_qkv);
   m.def("rope_qk_inplace", &rope_qk_inplace);
-  m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3);
-  m.def("flash_attn_bwd_v3", &flash_attn_bwd_v3);
   m.def("moe_topk", &moe_topk);
   m.def("moe_assign_slots", &moe_assign_slots);
   m.def("moe_dispatch_rows", &moe_dispatch_rows, pybind11::arg("x"),

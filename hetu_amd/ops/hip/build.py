@@ -28,7 +28,6 @@ SOURCES = [
     "gemm.hip",
     "attention.hip",
     "attention_v2.hip",
-    "attention_v3.hip",
     "attention_bwd_v3.hip",
     "attention_bwd_v2.hip",
     "quant.hip",
@@ -84,6 +83,9 @@ def build(verbose: bool = True) -> str:
         # make it a hard error
         "-Werror=return-type",
     ] + [f"-I{p}" for p in inc] + [f"-I{py_inc}", f"-I{HERE}"]
+    # every source may include any header of this directory
+    newest_h = max(os.path.getmtime(os.path.join(HERE, f))
+                   for f in os.listdir(HERE) if f.endswith(".h"))
     stale = []
     for src in srcs:
         base = os.path.basename(src).rsplit(".", 1)[0]
@@ -92,8 +94,7 @@ def build(verbose: bool = True) -> str:
         # skip if up to date
         if (os.path.exists(obj)
                 and os.path.getmtime(obj) > os.path.getmtime(src)
-                and os.path.getmtime(obj) > os.path.getmtime(
-                    os.path.join(HERE, "common.h"))):
+                and os.path.getmtime(obj) > newest_h):
             continue
         stale.append((src, obj))
 

@@ -234,6 +234,71 @@ class TestAttention:
                                  v.cpu().float(), True, scale)
         _close(o, orf, rtol=3e-2, atol=3e-2, what="fa spike")
 
+    @staticmethod
+    def _inputs(S, D=128, H=2, Hkv=2, B=1):
+        torch.manual_seed(0)
+        q = torch.randn(B, H, S, D, dtype=torch.bfloat16, device=dev())
+        k = torch.randn(B, Hkv, S, D, dtype=torch.bfloat16, device=dev())
+        v = torch.randn(B, Hkv, S, D, dtype=torch.bfloat16, device=dev())
+        return q, k, v, torch.randn_like(q), 1.0 / math.sqrt(D)
+
+    # S=64: single-tile duplicate-issue prologue; 256: wraps the 3-deep ring
+    # once; 300: clamped ragged-tail staging, two q-blocks; 1024: multi-block
+    @pytest.mark.parametrize("causal", [True, False])
+    @pytest.mark.parametrize("S", [64, 256, 300, 1024])
+    def test_bwd_v3_bit_equal_v2(self, S, causal):
+        """The two backward generations share their tile bodies and differ
+        only in staging, so impl=3 must reproduce impl=2 bit for bit."""
+        q, k, v, do, scale = self._inputs(S)
+        e = F.ext()
+        o, lse = e.flash_attn_fwd(q, k, v, causal, scale, 2)
+        g2 = e.flash_attn_bwd(do, q, k, v, o, lse, causal, scale, 2)
+        g3 = e.flash_attn_bwd(do, q, k, v, o, lse, causal, scale, 3)
+        for name, a, b in zip(("dq", "dk", "dv"), g3, g2):
+            assert torch.equal(a, b), f"{name}: impl=3 differs from impl=2"
+
+    def test_v1_at_d128(self):
+        """impl=1 at D=128: the HETU_AMD_FA1 bisect path."""
+        S, causal = 192, True
+        q, k, v, do, scale = self._inputs(S)
+        e = F.ext()
+        o, lse = e.flash_attn_fwd(q, k, v, causal, scale, 1)
+        orf, lser = F._attn_ref_fwd(q.cpu().float(), k.cpu().float(),
+                                    v.cpu().float(), causal, scale)
+        _close(o, orf, rtol=3e-2, atol=3e-2, what="fa1 fwd")
+        _close(lse, lser, rtol=1e-2, atol=1e-2, what="fa1 lse")
+        dq, dk, dv = e.flash_attn_bwd(do, q, k, v, o, lse, causal, scale, 1)
+        dqr, dkr, dvr = F._attn_ref_bwd(do.cpu().float(), q.cpu().float(),
+                                        k.cpu().float(), v.cpu().float(),
+                                        orf, lser, causal, scale)
+        _close(dq, dqr, rtol=5e-2, atol=5e-2, what="fa1 dq")
+        _close(dk, dkr, rtol=5e-2, atol=5e-2, what="fa1 dk")
+        _close(dv, dvr, rtol=5e-2, atol=5e-2, what="fa1 dv")
+
+    def test_unsupported_impl_raises(self):
+        """An explicit variant never falls back to another one."""
+        e = F.ext()
+        q, k, v, do, scale = self._inputs(64, H=4, Hkv=2)
+        o, lse = e.flash_attn_fwd(q, k, v, True, scale)
+        with pytest.raises(RuntimeError):     # v3 backward has no GQA
+            e.flash_attn_bwd(do, q, k, v, o, lse, True, scale, 3)
+        q, k, v, do, scale = self._inputs(64, D=64)
+        with pytest.raises(RuntimeError):     # v2 is D=128 only
+            e.flash_attn_fwd(q, k, v, True, scale, 2)
+        o, lse = e.flash_attn_fwd(q, k, v, True, scale)
+        with pytest.raises(RuntimeError):
+            e.flash_attn_bwd(do, q, k, v, o, lse, True, scale, 2)
+
+    def test_auto_bwd_is_v3(self, monkeypatch):
+        """Dense non-GQA D=128 takes the v3 backward by default."""
+        monkeypatch.setattr(F, "_FA_IMPL", 0)
+        q, k, v, do, scale = self._inputs(300)
+        o, lse = F.flash_attn_fwd(q, k, v, True, scale)
+        auto = F.flash_attn_bwd(do, q, k, v, o, lse, True, scale)
+        g3 = F.ext().flash_attn_bwd(do, q, k, v, o, lse, True, scale, 3)
+        for name, a, b in zip(("dq", "dk", "dv"), auto, g3):
+            assert torch.equal(a, b), f"{name}: automatic choice is not v3"
+
 
 class TestQuant:
     @pytest.mark.parametrize("qtype", ["int8", "nf4", "fp4"])
