@@ -1044,10 +1044,9 @@ class MatMulGradWOp(OpInterface):
                           w_pass={x.ndim - 1: 1})
 
     def compute(self, op, inputs, ctx):
+        from ...ops import functional as F
         gy, x = inputs
-        gy2 = gy.reshape(-1, gy.shape[-1])
-        x2 = x.reshape(-1, x.shape[-1])
-        return [torch.matmul(gy2.t(), x2)]
+        return [F.linear_wgrad(gy, x)]
 
 
 class MatMulGradBOp(OpInterface):

@@ -770,9 +770,9 @@ class FusedMLPGradOp(OpInterface):
         x2 = x.reshape(B * S, H)
         # dwproj = dy^T @ a; da->dgelu(+db1) fused; dwfc = dh^T @ x;
         # dx = dh @ wfc
-        dwproj = torch.matmul(dy2.t(), a).to(wproj.dtype)
+        dwproj = F.linear_wgrad(dy2, a).to(wproj.dtype)
         dh, db1 = F.dgelu_bgrad(dy2, wproj, aux)
-        dwfc = torch.matmul(dh.t(), x2).to(wfc.dtype)
+        dwfc = F.linear_wgrad(dh, x2).to(wfc.dtype)
         dx = torch.matmul(dh, wfc).reshape(B, S, H)
         outs = [dx, dwfc, db1, dwproj]
         if op.attrs.get("with_b2"):

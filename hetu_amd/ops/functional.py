@@ -552,13 +552,75 @@ def _attn_ref_bwd(dout, q, k, v, out, lse, causal, scale):
 # library (hipBLASLt via torch.matmul) for general shapes.
 # ---------------------------------------------------------------------------
 
-# GEMM routing: the hand-written MFMA kernel (ops/hip/gemm.hip, measured
-# ~910 TF bf16 on MI355X) vs hipBLASLt via torch.matmul (~1380-1550 TF on
-# the transformer shapes). Plain projection GEMMs default to the library
-# per the "library for plain GEMMs" rule; HETU_AMD_GEMM=hip forces the
-# hand kernel (used by tests/microbenchmarks, and the target of the
-# 256^2 8-phase upgrade).
+# GEMM routing.  Three GEMMs per linear layer (profiles/r03_wgrad_gemm.md):
+#   forward x @ W^T (TN) and dgrad gy @ W (NN): hipBLASLt via torch.matmul /
+#     F.linear (~1.4-1.6 PF/s on the transformer shapes).  The 128^2 hand
+#     kernel (ops/hip/gemm.hip, ~910 TF) loses there; HETU_AMD_GEMM=hip
+#     forces it for tests and microbenchmarks.
+#   wgrad gy^T @ x (NT over tokens): linear_wgrad() below, which picks
+#     between the library and the 256^2 transposed-read hand kernel
+#     (ops/hip/gemm_wgrad.hip) per shape.
 _HETU_GEMM = os.environ.get("HETU_AMD_GEMM", "blas")  # hip | blas
+_HETU_WGRAD = os.environ.get("HETU_AMD_WGRAD", "auto")  # auto | hip | blas
+_WGRAD_IMPLS = ("auto", "hip", "blas")
+
+
+def _wgrad_hip_eligible(gy2, x2) -> bool:
+    """What ops/hip/gemm_wgrad.hip takes: full 256x256 output tiles and
+    whole 64-token K-tiles of contiguous bf16 GPU operands."""
+    return (gy2.is_cuda and x2.is_cuda and gy2.device == x2.device
+            and gy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16
+            and gy2.is_contiguous() and x2.is_contiguous()
+            and gy2.shape[0] == x2.shape[0] and gy2.shape[0] > 0
+            and gy2.shape[0] % 64 == 0
+            and gy2.shape[1] > 0 and gy2.shape[1] % 256 == 0
+            and x2.shape[1] > 0 and x2.shape[1] % 256 == 0)
+
+
+def _wgrad_auto_hip(T: int, N: int, K: int) -> bool:
+    """Shape classes where the hand kernel beat hipBLASLt with
+    non-overlapping min-max ranges in scripts/bench_wgrad.py
+    (profiles/r03_wgrad_gemm.md, per-shape table): outputs of 256, 768 and
+    1024 tiles of 256x256 (16x16, 48x16, 64x16, 16x64), at T = 2048, 8192
+    and 32768 tokens (1.17-1.26x).  What those have in common is the rule:
+    whole rounds of the 256 CUs at one block per CU, and a tile grid the
+    kernel folds into 8x4 rectangles per XCD (N/256 % 8 == 0, K/256 % 4
+    == 0) so the operand panels are shared through L2.  Other multiples of
+    256 tiles (512, 1280, ...) have the same properties but were not
+    timed: that part is extrapolated.  A partial last round (the library's
+    stream-K balances it, this kernel does not), grids without the fold
+    and shorter contractions stay on the library."""
+    tn, tk = N // 256, K // 256
+    return tn % 8 == 0 and tk % 4 == 0 and (tn * tk) % 256 == 0 and T >= 2048
+
+
+def linear_wgrad(gy, x, impl=None):
+    """Weight gradient of y = x @ W^T: dW [N, K] = gy[..., N]^T @ x[..., K]
+    over the flattened leading (token) dims.
+
+    impl: "blas" = torch.matmul (hipBLASLt); "hip" = the hand kernel, an
+    error if the input is not eligible (never a fallback); "auto" = the
+    hand kernel where it measured faster, else the library.  None takes
+    HETU_AMD_WGRAD (default auto)."""
+    impl = _HETU_WGRAD if impl is None else impl
+    if impl not in _WGRAD_IMPLS:
+        raise ValueError(f"linear_wgrad: impl must be one of {_WGRAD_IMPLS}, "
+                         f"got {impl!r}")
+    gy2 = gy.reshape(-1, gy.shape[-1])
+    x2 = x.reshape(-1, x.shape[-1])
+    if impl == "hip":
+        if not _wgrad_hip_eligible(gy2, x2):
+            raise RuntimeError(
+                "linear_wgrad(impl='hip') needs contiguous bf16 GPU operands "
+                "with N % 256 == 0, K % 256 == 0 and T % 64 == 0; got "
+                f"gy {tuple(gy2.shape)} {gy2.dtype} x {tuple(x2.shape)} "
+                f"{x2.dtype} contiguous={gy2.is_contiguous()},"
+                f"{x2.is_contiguous()} device={gy2.device}")
+        return ext().gemm_wgrad_bf16(gy2, x2)
+    if (impl == "auto" and _gpu(gy2, x2) and _wgrad_hip_eligible(gy2, x2)
+            and _wgrad_auto_hip(gy2.shape[0], gy2.shape[1], x2.shape[1])):
+        return ext().gemm_wgrad_bf16(gy2, x2)
+    return torch.matmul(gy2.t(), x2)
 
 
 def linear(x, w, bias=None, trans_w: bool = True):

@@ -92,6 +92,8 @@ void adam_step(torch::Tensor param32, torch::Tensor grad, torch::Tensor m,
                torch::Tensor out16, torch::Tensor bc_dev);
 // gemm.hip
 torch::Tensor gemm_bf16(torch::Tensor x, torch::Tensor w, bool trans_w);
+// gemm_wgrad.hip
+torch::Tensor gemm_wgrad_bf16(torch::Tensor gy, torch::Tensor x);
 // quant.hip
 std::vector<torch::Tensor> quantize_blockwise(torch::Tensor x,
                                               std::string qtype,
@@ -193,6 +195,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_bwd", &embedding_bwd);
   m.def("adam_step", &adam_step);
   m.def("gemm_bf16", &gemm_bf16);
+  m.def("gemm_wgrad_bf16", &gemm_wgrad_bf16);
   m.def("quantize_blockwise", &quantize_blockwise);
   m.def("dequantize_blockwise", &dequantize_blockwise);
   m.def("galvatron_dp", &galvatron_dp);

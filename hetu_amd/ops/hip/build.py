@@ -26,6 +26,7 @@ SOURCES = [
     "embedding.hip",
     "adam.hip",
     "gemm.hip",
+    "gemm_wgrad.hip",
     "attention.hip",
     "attention_v2.hip",
     "attention_bwd_v3.hip",
