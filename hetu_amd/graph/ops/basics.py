@@ -992,6 +992,10 @@ class MatMul2DOp(OpInterface):
             a = a.transpose(-1, -2)
         if op.attrs.get("trans_b", False):
             b = b.transpose(-1, -2)
+        elif not op.attrs.get("trans_a", False) and b.dim() == 2:
+            # a @ b with b [N, K] as stored: the dgrad form (linear_dx)
+            from ...ops import functional as F
+            return [F.linear_dgrad(a, b)]
         return [torch.matmul(a, b)]
 
     def gradient(self, op, g):

@@ -773,7 +773,7 @@ class FusedMLPGradOp(OpInterface):
         dwproj = F.linear_wgrad(dy2, a).to(wproj.dtype)
         dh, db1 = F.dgelu_bgrad(dy2, wproj, aux)
         dwfc = F.linear_wgrad(dh, x2).to(wfc.dtype)
-        dx = torch.matmul(dh, wfc).reshape(B, S, H)
+        dx = F.linear_dgrad(dh, wfc).reshape(B, S, H)
         outs = [dx, dwfc, db1, dwproj]
         if op.attrs.get("with_b2"):
             outs.append(F.colsum(dy2).to(dy.dtype))

@@ -553,10 +553,14 @@ def _attn_ref_bwd(dout, q, k, v, out, lse, causal, scale):
 # ---------------------------------------------------------------------------
 
 # GEMM routing.  Three GEMMs per linear layer (profiles/r03_wgrad_gemm.md):
-#   forward x @ W^T (TN) and dgrad gy @ W (NN): hipBLASLt via torch.matmul /
-#     F.linear (~1.4-1.6 PF/s on the transformer shapes).  The 128^2 hand
-#     kernel (ops/hip/gemm.hip, ~910 TF) loses there; HETU_AMD_GEMM=hip
-#     forces it for tests and microbenchmarks.
+#   forward x @ W^T (TN): hipBLASLt via F.linear (~1.6 PF/s on the
+#     transformer shapes).  The 128^2 hand kernel (ops/hip/gemm.hip, ~910
+#     TF) loses there; HETU_AMD_GEMM=hip forces it for tests and
+#     microbenchmarks.
+#   dgrad gy @ W (NN): linear_dgrad() below.  The library's NN form runs at
+#     ~1.35 PF/s, so for large shapes W is copied to W^T
+#     (ops/hip/transpose.hip) and the forward's TN form is called instead
+#     (profiles/r04_dgrad_layout.md).
 #   wgrad gy^T @ x (NT over tokens): linear_wgrad() below, which picks
 #     between the library and the 256^2 transposed-read hand kernel
 #     (ops/hip/gemm_wgrad.hip) per shape.
@@ -621,6 +625,74 @@ def linear_wgrad(gy, x, impl=None):
             and _wgrad_auto_hip(gy2.shape[0], gy2.shape[1], x2.shape[1])):
         return ext().gemm_wgrad_bf16(gy2, x2)
     return torch.matmul(gy2.t(), x2)
+
+
+_HETU_DGRAD = os.environ.get("HETU_AMD_DGRAD", "auto")  # auto|transposed|blas
+_DGRAD_IMPLS = ("auto", "transposed", "blas")
+
+
+def _dgrad_transposed_eligible(gy, w) -> bool:
+    """What the transposed route takes: a contiguous 2-D bf16/fp16 weight
+    on the GPU that holds gy, of gy's dtype (ops/hip/transpose.hip moves
+    2-byte elements)."""
+    return (gy.is_cuda and w.is_cuda and gy.device == w.device
+            and w.dim() == 2 and w.is_contiguous() and gy.dim() >= 1
+            and w.dtype in (torch.bfloat16, torch.float16)
+            and gy.dtype == w.dtype and gy.shape[-1] == w.shape[0])
+
+
+def _dgrad_auto_transposed(T: int, N: int, K: int) -> bool:
+    """Shape classes where transpose + TN GEMM beat the library's NN GEMM
+    with non-overlapping min-max ranges in scripts/bench_dgrad.py
+    (profiles/r04_dgrad_layout.md, per-shape table).
+
+    Measured: (N -> K) 12288->4096, 4096->4096, 16384->4096 and 4096->16384
+    at T = 32768, 16384 and 8192 tokens, and the LM head 50304->4096 at
+    T = 32768: all thirteen rows win, 1.08-1.16x, in three runs.  At
+    T = 4096 the four layer shapes win by 2-9 % in two runs and 16384->4096
+    overlaps in the third; at T = 2048 the transpose costs more than the
+    faster GEMM form saves on all four.
+    What the winning rows have in common is the rule: at least 8192 tokens
+    and a weight of at least 4096 x 4096 whose sides are multiples of 8
+    (the transpose kernel's 16-byte path).  Token counts between the
+    measured ones, other weight sizes of that class, and the LM head below
+    T = 32768 pass the rule without having been timed: that part is
+    extrapolated.  T = 4096 is left on the library because its win did
+    not repeat."""
+    return (T >= 8192 and N >= 4096 and K >= 4096
+            and N % 8 == 0 and K % 8 == 0)
+
+
+def linear_dgrad(gy, w, impl=None):
+    """Input gradient of y = x @ W^T: dx[..., K] = gy[..., N] @ w[N, K].
+
+    impl: "blas" = torch.matmul(gy, w) (hipBLASLt NN form); "transposed" =
+    copy w to Wt [K, N] with the HIP transpose kernel and run the forward's
+    TN form F.linear(gy, Wt), an error if the input is not eligible (never
+    a fallback); "auto" = the transposed route where it measured faster,
+    else the library, and always the library on CPU.  None takes
+    HETU_AMD_DGRAD (default auto).  The copy lives only inside the call:
+    nothing is cached, so it can never be stale."""
+    impl = _HETU_DGRAD if impl is None else impl
+    if impl not in _DGRAD_IMPLS:
+        raise ValueError(f"linear_dgrad: impl must be one of {_DGRAD_IMPLS}, "
+                         f"got {impl!r}")
+    if impl == "blas":
+        return torch.matmul(gy, w)
+    eligible = _dgrad_transposed_eligible(gy, w)
+    if impl == "transposed" and not eligible:
+        raise RuntimeError(
+            "linear_dgrad(impl='transposed') needs a contiguous 2-D bf16 or "
+            "fp16 GPU weight of gy's dtype and device; got "
+            f"gy {tuple(gy.shape)} {gy.dtype} {gy.device} w {tuple(w.shape)} "
+            f"{w.dtype} {w.device} contiguous={w.is_contiguous()}")
+    if impl == "transposed" or (
+            eligible and _dgrad_auto_transposed(
+                gy.numel() // max(gy.shape[-1], 1), w.shape[0], w.shape[1])):
+        gy2 = gy.reshape(-1, gy.shape[-1])
+        dx = torch.nn.functional.linear(gy2, ext().transpose2d(w))
+        return dx.reshape(*gy.shape[:-1], w.shape[1])
+    return torch.matmul(gy, w)
 
 
 def linear(x, w, bias=None, trans_w: bool = True):
@@ -913,7 +985,7 @@ def dgelu_bgrad(dy2d, w, aux):
             _LT_BWD[0] = False
             print("[hetu_amd] hipBLASLt DGELU_BGRAD epilogue unavailable, "
                   "composing the MLP backward")
-    da = torch.matmul(dy2d, w.to(dy2d.dtype))
+    da = linear_dgrad(dy2d, w.to(dy2d.dtype))
     dh = gelu_bwd(da, aux)
     return dh, colsum(dh).to(dh.dtype)
 

@@ -27,6 +27,7 @@ SOURCES = [
     "adam.hip",
     "gemm.hip",
     "gemm_wgrad.hip",
+    "transpose.hip",
     "attention.hip",
     "attention_v2.hip",
     "attention_bwd_v3.hip",
