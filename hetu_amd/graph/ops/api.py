@@ -333,6 +333,14 @@ def softmax(a, dim=-1):
     return _cg().make_op(N.SoftmaxOp(), [a], {"dim": dim}).output()
 
 
+def moe_gate(logits, k: int):
+    """Fused MoE gate: logits [N, E] -> (probs [N, E], aux, z) with aux the
+    load-balance loss and z the router z-loss, both fp32 scalars."""
+    from .moe_ops import MoEGateOp
+    op = _cg().make_op(MoEGateOp(), [logits], {"k": int(k)}, name="moe_gate")
+    return op.output(0), op.output(1), op.output(2)
+
+
 _DROPOUT_SEED = [12345]
 _DROPOUT_OFFSET = [0]
 

@@ -211,3 +211,81 @@ class MoECombineGradOp(OpInterface):
         else:
             d_eo = d_recv.reshape(El, P * C, -1)
         return [d_eo, dwk]
+
+
+class MoEGateOp(OpInterface):
+    """Fused learned gate: logits [N, E] -> probs [N, E] (softmax, logits'
+    dtype), aux [] fp32 (load-balance loss), z [] fp32 (router z-loss), and
+    the saved lse [N] fp32, cnt [E] int32 (see ops.functional.moe_gate for
+    the definitions).  MoEDispatchOp keeps routing from probs; its top-k is
+    the one cnt counts."""
+    type = "MoEGate"
+
+    def infer_meta(self, attrs, inputs):
+        lg = inputs[0]
+        N, E = lg.shape
+        return [TensorMeta([N, E], lg.dtype),
+                TensorMeta([], torch.float32),
+                TensorMeta([], torch.float32),
+                TensorMeta([N], torch.float32),
+                TensorMeta([E], torch.int32)]
+
+    def deduce_states(self, op):
+        lg = op.inputs[0]
+        for t in op.outputs:
+            t.device_group = lg.device_group
+        src = lg.ds
+        if src is None:
+            return
+        if src.partial > 1 or src.get_dim(1) > 1:
+            raise ValueError(
+                f"moe_gate: logits must be whole rows of tokens, got {src}")
+        probs, aux, z, lse, cnt = op.outputs
+        probs.ds = lse.ds = src
+        # statistics are per rank over the rank's own tokens: the token
+        # split (dim 0) becomes a partial, i.e. the global value is the sum
+        # over ranks; a duplicate factor stays a duplicate
+        states = {(-2 if d == 0 else d): n for d, n in src.states.items()}
+        order = [(-2 if d == 0 else d) for d in src.order]
+        aux.ds = z.ds = cnt.ds = DistributedStates(src.device_num, states,
+                                                   order)
+
+    def compute(self, op, inputs, ctx):
+        probs, _, _, lse, _, cnt, aux, z = F.moe_gate(inputs[0],
+                                                      op.attrs["k"])
+        return [probs, aux, z, lse, cnt]
+
+    def gradient(self, op, g):
+        ups = list(g[:3])
+        if all(u is None for u in ups):
+            return [None]
+        gr = _g(op.outputs[0])
+        attrs = dict(op.attrs)
+        attrs["has"] = [u is not None for u in ups]
+        bwd = _make(gr, MoEGateGradOp(),
+                    [u for u in ups if u is not None]
+                    + [op.inputs[0], op.outputs[3], op.outputs[4]],
+                    attrs, name="moe_gate_grad")
+        return [bwd.output()]
+
+
+class MoEGateGradOp(OpInterface):
+    """inputs: the present ones of (g_probs, g_aux, g_z) as flagged by
+    attrs["has"], then logits, lse, cnt -> dlogits [N, E]."""
+    type = "MoEGateGrad"
+
+    def infer_meta(self, attrs, inputs):
+        lg = inputs[-3]
+        return [TensorMeta(lg.shape, lg.dtype)]
+
+    def deduce_states(self, op):
+        lg = op.inputs[-3]
+        op.outputs[0].ds = lg.ds
+        op.outputs[0].device_group = lg.device_group
+
+    def compute(self, op, inputs, ctx):
+        it = iter(inputs[:-3])
+        g_probs, g_aux, g_z = [next(it) if h else None
+                               for h in op.attrs["has"]]
+        logits, lse, cnt = inputs[-3:]
+        return [F.moe_gate_grad(g_probs, g_aux, g_z, logits, lse, cnt)]

@@ -45,6 +45,10 @@ class GPTConfig:
     moe_experts: int = 0
     moe_k: int = 2
     moe_capacity: float = 1.25
+    # weights of the load-balance loss and the router z-loss, each summed
+    # over the MoE layers and added to the LM loss (0 = plain softmax gate)
+    moe_aux_coef: float = 0.0
+    moe_z_coef: float = 0.0
 
 
 GPT_CONFIGS = {
@@ -153,7 +157,9 @@ class GPTMoEMLP(Module):
         self.moe = MoEMLP(cfg.hidden, cfg.ffn_hidden, cfg.moe_experts,
                           spec=spec if spec.num_devices > 1 else None,
                           k=cfg.moe_k, capacity_factor=cfg.moe_capacity,
-                          dtype=dtype, name=f"h{layer_idx}.moe")
+                          dtype=dtype, name=f"h{layer_idx}.moe",
+                          aux_loss_coef=cfg.moe_aux_coef,
+                          z_loss_coef=cfg.moe_z_coef)
         self.hidden = cfg.hidden
 
     def forward(self, x):
@@ -282,7 +288,33 @@ class GPTLMHeadModel(Module):
             return None, logits
         per_tok = vocab_parallel_cross_entropy(logits, labels, cfg.vocab)
         loss = ht.reduce_mean(per_tok)
+        self.lm_loss, self.aux_loss, self.z_loss = loss, None, None
+        if cfg.moe_experts > 0 and (cfg.moe_aux_coef or cfg.moe_z_coef):
+            loss = self._add_gate_losses(loss)
         return loss, logits
+
+    def _add_gate_losses(self, loss):
+        """loss + moe_aux_coef * sum_layers aux + moe_z_coef * sum_layers z
+        (fp32 scalars, like the LM loss).  Each rank's statistics cover its
+        own tokens; scaled by 1 / (token split) they are partial sums of
+        the mean over ranks, the same representation the LM loss has."""
+        cfg = self.cfg
+        ds_tok = self.spec.ds_tokens(0)
+        split = ds_tok.get_dim(0) if ds_tok is not None else 1
+
+        def total(ts):
+            t = ts[0] if len(ts) == 1 else ht.add_n(ts)
+            return ht.mul(t, 1.0 / split) if split > 1 else t
+
+        moes = [blk.mlp.moe for blk in self.layers]
+        self.aux_loss = total([m.aux_loss for m in moes])
+        self.z_loss = total([m.z_loss for m in moes])
+        # add_n, not add: with tokens split over ranks all terms are partial
+        # sums with one layout, which the n-ary sum keeps as it is
+        terms = [loss] + [ht.mul(t, float(coef)) for coef, t in
+                          ((cfg.moe_aux_coef, self.aux_loss),
+                           (cfg.moe_z_coef, self.z_loss)) if coef]
+        return ht.add_n(terms)
 
 
 def build_gpt_train_graph(cfg: GPTConfig, micro_batch: int, seq_len: int,
@@ -310,17 +342,28 @@ def build_gpt_train_graph(cfg: GPTConfig, micro_batch: int, seq_len: int,
                                recompute=recompute)
         loss, _ = model(input_ids, labels)
         loss_report = loss
+        # for logging: the LM part and the gate losses summed over layers
+        # (None without a gate-loss coefficient)
+        parts = {"lm_loss": model.lm_loss, "aux_loss": model.aux_loss,
+                 "z_loss": model.z_loss}
         if spec.num_devices > 1:
             loss_report = ht.comm(
                 loss, spec._ds({-1: spec.num_devices}, [-1]),
                 name="loss_allreduce")
+            for key, t in parts.items():
+                if t is not None and t is not loss:
+                    parts[key] = ht.comm(
+                        t, spec._ds({-1: spec.num_devices}, [-1]),
+                        name=f"{key}_allreduce")
+        if parts["lm_loss"] is loss:
+            parts["lm_loss"] = loss_report
         opt = Adam(lr=lr, zero=zero, hetero=hetero)
         train_op = opt.minimize(loss)
     finally:
         pop_graph()
     return g, {"input_ids": input_ids, "labels": labels,
                "loss": loss_report, "train_op": train_op,
-               "optimizer": opt, "model": model}
+               "optimizer": opt, "model": model, **parts}
 
 
 def build_gpt_pipeline_stage(cfg: GPTConfig, pspec, micro_batch: int,
@@ -329,6 +372,11 @@ def build_gpt_pipeline_stage(cfg: GPTConfig, pspec, micro_batch: int,
                              zero: bool = False):
     """This rank's pipeline-stage subgraph (see parallel.pipeline)."""
     from ..parallel.pipeline import StageModule
+    if cfg.moe_experts > 0 and (cfg.moe_aux_coef or cfg.moe_z_coef):
+        raise NotImplementedError(
+            "moe_aux_coef / moe_z_coef are not supported in pipeline "
+            "stages: a gate loss on a stage other than the last needs a "
+            "second backward seed next to the incoming activation gradient")
     B, S = micro_batch, seq_len
     sid = pspec.my_stage()
     spec = pspec.stage_spec(sid)

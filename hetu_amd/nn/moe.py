@@ -30,12 +30,23 @@ class MoEMLP(Module):
                  params; HashGate semantics for static-shape graphs)
       "random" — static pseudo-random token->expert assignment (BASE-like
                  balanced random routing, fixed at build time)
+
+    aux_loss_coef / z_loss_coef (reference TopGate.py balance_loss): a
+    non-zero coefficient switches the learned gates to the fused gate op
+    (ht.moe_gate), which also yields the load-balance loss and the router
+    z-loss; after forward() they are self.aux_loss / self.z_loss (fp32
+    scalar graph tensors, per rank over the rank's own tokens; None on the
+    plain softmax path), self.gate_counts the per-expert choice counts.  The layer does not add them to anything: the
+    model weighs them with the coefficients.  fused_gate forces the choice
+    (None = fused iff a coefficient is non-zero).
     """
 
     def __init__(self, hidden: int, ffn_hidden: int, num_experts: int,
                  spec: Optional[ParallelSpec] = None, k: int = 2,
                  capacity_factor: float = 1.25, dtype=torch.float32,
-                 gate_type: str = "topk", name: str = "moe"):
+                 gate_type: str = "topk", name: str = "moe",
+                 aux_loss_coef: float = 0.0, z_loss_coef: float = 0.0,
+                 fused_gate: Optional[bool] = None):
         super().__init__()
         spec = spec or ParallelSpec()
         self.spec = spec
@@ -47,6 +58,20 @@ class MoEMLP(Module):
         elif gate_type in ("hash", "random"):
             k = 1
         self.k = k
+        self.aux_loss_coef = float(aux_loss_coef)
+        self.z_loss_coef = float(z_loss_coef)
+        learned = gate_type in ("topk", "switch")
+        if not learned and (self.aux_loss_coef or self.z_loss_coef
+                            or fused_gate):
+            raise ValueError(
+                f"gate_type {gate_type!r} has no learned gate: no "
+                "load-balance / z-loss and no fused gate")
+        if fused_gate is None:
+            fused_gate = bool(self.aux_loss_coef or self.z_loss_coef)
+        self.fused_gate = bool(fused_gate)
+        self.aux_loss = None
+        self.z_loss = None
+        self.gate_counts = None    # [E] int32 choices per expert (fused gate)
         self.dtype = dtype
         self.name = name
         self.capacity_factor = capacity_factor
@@ -100,7 +125,12 @@ class MoEMLP(Module):
         C = max(1, int(self.capacity_factor * self.k * N / self.E))
         if self.gate_type in ("topk", "switch"):
             logits = ht.linear(x, self.gate)      # [N, E]
-            probs = ht.softmax(logits, dim=-1)
+            if self.fused_gate:
+                probs, self.aux_loss, self.z_loss = ht.moe_gate(logits,
+                                                                self.k)
+                self.gate_counts = probs.producer.outputs[4]
+            else:
+                probs = ht.softmax(logits, dim=-1)
         else:
             probs = self._static_gate(int(N))
         g = x.graph

@@ -1157,3 +1157,81 @@ def moe_combine_rows_bwd(gy: torch.Tensor, recv: torch.Tensor,
         out.copy_(d_recv)
         d_recv = out
     return d_recv, dwk
+
+
+# ---------------------------------------------------------------------------
+# Fused MoE gate (moe.hip (h)): softmax + top-k + the load-balance and router
+# z-loss statistics in one pass.  For logits [N, E] and K choices:
+#   lse[t]  = logsumexp_e float(logits[t, e])       p32 = exp(logits - lse)
+#   probs   = p32 rounded once to the logits' dtype
+#   idx, w  = top-K of the stored probs row (value desc, expert index asc,
+#             compared as fp32) -- what moe_route(probs, C, K) selects
+#   cnt[e]  = #{(t, k): idx[t, k] == e}, before capacity dropping
+#   psum[e] = sum_t p32[t, e]
+#   aux     = E / N^2 * sum_e psum[e] * cnt[e]      (value K when uniform)
+#   z       = 1 / N * sum_t lse[t]^2
+# Backward, cnt held constant:
+#   dp      = g_probs + g_aux * E / N^2 * cnt
+#   dlogits = p32 * (dp - <p32, dp>) + g_z * 2 / N * lse * p32
+# The extension entry points are moe_gate_fwd / moe_gate_grad
+# (moe_gate_bwd is the dispatch gate scatter above).
+# ---------------------------------------------------------------------------
+
+MOE_GATE_MAX_BLOCKS = 1024     # grid cap of the fused gate's forward kernel
+
+
+def moe_gate(logits: torch.Tensor, K: int):
+    """logits [N, E] -> (probs [N, E], idx [N, K] int64, w [N, K] fp32,
+    lse [N] fp32, psum [E] fp32, cnt [E] int32, aux [] fp32, z [] fp32)."""
+    N, E = logits.shape
+    if not 1 <= K <= E:
+        raise ValueError(f"moe_gate: need 1 <= K <= E, got K={K}, E={E}")
+    if N >= 1 and _moe_hip(K, E, logits):
+        return tuple(ext().moe_gate_fwd(logits.contiguous(), K))
+    xf = logits.float()
+    lse = torch.logsumexp(xf, dim=-1)
+    p32 = torch.softmax(xf, dim=-1)
+    probs = p32.to(logits.dtype)
+    # stable descending sort == (value desc, index asc); topk leaves the
+    # tie order unspecified
+    w, idx = torch.sort(probs.float(), dim=-1, descending=True, stable=True)
+    w, idx = w[:, :K].contiguous(), idx[:, :K].contiguous()
+    cnt = torch.zeros(E, dtype=torch.int32, device=logits.device)
+    cnt.scatter_add_(0, idx.reshape(-1),
+                     torch.ones(N * K, dtype=torch.int32,
+                                device=logits.device))
+    psum = colsum(p32)        # no at::native column reduce on a GPU
+    # the two scalars are formed in fp64 and rounded once, as in the kernel
+    aux = ((psum.double() * cnt.double()).sum() * (E / float(N * N))).float()
+    z = ((lse.double() ** 2).sum() / N).float()
+    return probs, idx, w, lse, psum, cnt, aux, z
+
+
+def moe_gate_grad(g_probs: Optional[torch.Tensor],
+                  g_aux: Optional[torch.Tensor],
+                  g_z: Optional[torch.Tensor], logits: torch.Tensor,
+                  lse: torch.Tensor, cnt: torch.Tensor) -> torch.Tensor:
+    """Backward of moe_gate -> dlogits [N, E].  g_probs [N, E], g_aux and
+    g_z (one-element tensors, read on the device) may each be None (zero)."""
+    N, E = logits.shape
+    if N >= 1 and _moe_hip(1, E, logits):
+        def scalar(t):
+            return None if t is None else \
+                t.to(device=logits.device, dtype=torch.float32).reshape(())
+        gp = None if g_probs is None else \
+            g_probs.to(logits.dtype).contiguous()
+        return ext().moe_gate_grad(gp, scalar(g_aux), scalar(g_z),
+                                   logits.contiguous(),
+                                   lse.float().contiguous(),
+                                   cnt.to(torch.int32).contiguous())
+    xf = logits.float()
+    l = lse.float().unsqueeze(-1)
+    p = torch.exp(xf - l)
+    dp = torch.zeros_like(xf) if g_probs is None else g_probs.float()
+    if g_aux is not None:
+        dp = dp + (g_aux.float().reshape(()) * (E / float(N * N))) \
+            * cnt.float()
+    dl = p * (dp - (p * dp).sum(-1, keepdim=True))
+    if g_z is not None:
+        dl = dl + (g_z.float().reshape(()) * (2.0 / N)) * l * p
+    return dl.to(logits.dtype)

@@ -155,6 +155,14 @@ std::vector<torch::Tensor> moe_combine_rows_bwd(
     torch::Tensor gy, torch::Tensor recv, torch::Tensor wk,
     torch::Tensor pos, torch::Tensor slot_of,
     c10::optional<torch::Tensor> out);
+int64_t moe_gate_max_blocks();
+int64_t moe_gate_tokens_per_block(int64_t E);
+std::vector<torch::Tensor> moe_gate_fwd(torch::Tensor logits, int64_t K);
+torch::Tensor moe_gate_grad(c10::optional<torch::Tensor> g_probs,
+                            c10::optional<torch::Tensor> g_aux,
+                            c10::optional<torch::Tensor> g_z,
+                            torch::Tensor logits, torch::Tensor lse,
+                            torch::Tensor cnt);
 
 // embed_cache.cpp
 void register_embed_cache(pybind11::module& m);
@@ -225,4 +233,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine_rows_bwd", &moe_combine_rows_bwd, pybind11::arg("gy"),
         pybind11::arg("recv"), pybind11::arg("wk"), pybind11::arg("pos"),
         pybind11::arg("slot_of"), pybind11::arg("out") = pybind11::none());
+  m.def("moe_gate_max_blocks", &moe_gate_max_blocks);
+  m.def("moe_gate_tokens_per_block", &moe_gate_tokens_per_block);
+  m.def("moe_gate_fwd", &moe_gate_fwd);
+  m.def("moe_gate_grad", &moe_gate_grad);
 }

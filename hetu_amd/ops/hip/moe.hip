@@ -1,5 +1,7 @@
 // MoE routing / layout kernels: top-k gate selection, capacity slot
 // assignment, and the dispatch / combine row movement with their backwards.
+// Section (h) adds the fused gate: softmax + top-k + the load-balance and
+// router z-loss statistics, forward and backward.
 // Reference parity: hetu/impl/kernel TopKIdx.cu, LayoutTransform.cu,
 // ReverseLayoutTransform; written for wave64 from scratch.
 //
@@ -354,6 +356,398 @@ __global__ void moe_combine_bwd_kernel(const T* __restrict__ gy,
   }
 }
 
+// ---------------------------------------------------------------------------
+// (h) fused gate: softmax + top-k + load-balance / z-loss statistics.
+//   lse[t]  = logsumexp_e logits[t,e]          p32 = exp(logits - lse)
+//   probs   = p32 rounded once to T            idx, w = moe_topk(probs)
+//   psum[e] = sum_t p32[t,e]                   cnt[e] = #{(t,k): idx[t,k]==e}
+//   aux = E/N^2 * sum_e psum[e]*cnt[e]         z = 1/N * sum_t lse[t]^2
+// A group of gw lanes (a power of two, a whole wave once E > 32) owns a
+// token; lane l of the group owns experts l, l+gw, ...  For E <= 256 the row
+// lives in registers (R = 1, 2 or 4 elements per lane): one read of logits,
+// one write of probs, and the K selection rounds of moe_topk run on the
+// rounded values without touching memory.  Larger E takes the looping
+// kernel, which re-reads the row as moe_topk does.  The grid is capped at
+// GATE_MAX_BLOCKS and grid-strided.  Each group keeps an fp32 psum row and
+// an int cnt row in LDS ([groups][E] each; 64 KiB at E = 2048); only the
+// owning lane touches a column, so there are no conflicts and no atomics.
+// The block adds its groups' rows in group order into one row of part_p /
+// part_c / part_z; moe_gate_colsum_kernel sums the partial rows in a fixed
+// order and (one block, E <= 64) also forms the scalars, else
+// moe_gate_scalars_kernel does.  Grid and group shape depend on N and E
+// only, so every output is a pure function of the inputs.
+// ---------------------------------------------------------------------------
+constexpr int GATE_BLOCK = 256;
+constexpr int GATE_WAVES = GATE_BLOCK / WAVE;
+constexpr int GATE_MAX_BLOCKS = 1024;
+constexpr int GATE_REG_E = 256;                // largest E held in registers
+
+// the value half of a topk_key (values here are probabilities, never -0)
+DEV float topk_key_value(u64 key) {
+  const u32 b = (u32)(key >> 32);
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
+}
+
+// what st1 stores, read back
+DEV float stored(const float*, float v) { return v; }
+DEV float stored(const bf16*, float v) { return bf2f(f2bf(v)); }
+DEV float stored(const __half*, float v) {
+  return __half2float(__float2half_rn(v));
+}
+
+// fixed-order fp64 block sum (<= 16 waves; smem holds 16 doubles); the
+// result is valid on thread 0
+DEV double block_sum_f64(double x, double* smem) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int nwaves = (blockDim.x + WAVE - 1) >> 6;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, WAVE);
+  if (lane == 0) smem[wid] = x;
+  __syncthreads();
+  double r = 0.0;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < nwaves; ++i) r += smem[i];
+  __syncthreads();
+  return r;
+}
+
+// butterflies over a group of gw lanes: every lane gets the same bits
+DEV float group_max(float x, int gw) {
+  for (int off = gw >> 1; off > 0; off >>= 1)
+    x = fmaxf(x, __shfl_xor(x, off, WAVE));
+  return x;
+}
+DEV float group_sum(float x, int gw) {
+  for (int off = gw >> 1; off > 0; off >>= 1) x += __shfl_xor(x, off, WAVE);
+  return x;
+}
+DEV u64 group_max(u64 x, int gw) {
+  for (int off = gw >> 1; off > 0; off >>= 1) {
+    const u64 o = __shfl_xor(x, off, WAVE);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+
+// lanes per token of the forward kernels
+int gate_group_width(int64_t E) {
+  int gw = 1;
+  while (gw < E && gw < WAVE) gw <<= 1;
+  return gw;
+}
+
+// block epilogue: rows of the block's groups -> one partial row, in group
+// order; then the groups' z sums through the same LDS
+DEV void gate_block_partials(float* lds, int groups, int E, int gid,
+                             bool leader, float zacc,
+                             float* __restrict__ part_p,
+                             int* __restrict__ part_c,
+                             float* __restrict__ part_z) {
+  __syncthreads();
+  const float* P = lds;
+  const int* Cn = reinterpret_cast<const int*>(lds + (size_t)groups * E);
+  for (int e = threadIdx.x; e < E; e += GATE_BLOCK) {
+    float ps = P[e];
+    int cs = Cn[e];
+    for (int i = 1; i < groups; ++i) {
+      ps += P[(size_t)i * E + e];
+      cs += Cn[(size_t)i * E + e];
+    }
+    part_p[(int64_t)blockIdx.x * E + e] = ps;
+    part_c[(int64_t)blockIdx.x * E + e] = cs;
+  }
+  __syncthreads();                             // rows consumed: reuse for z
+  if (leader) lds[gid] = zacc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float zs = lds[0];
+    for (int i = 1; i < groups; ++i) zs += lds[i];
+    part_z[blockIdx.x] = zs;
+  }
+}
+
+template <typename T, int R>
+__global__ __launch_bounds__(GATE_BLOCK)
+void moe_gate_fwd_kernel(const T* __restrict__ logits, T* __restrict__ probs,
+                         int64_t* __restrict__ idx, float* __restrict__ w,
+                         float* __restrict__ lse, float* __restrict__ part_p,
+                         int* __restrict__ part_c, float* __restrict__ part_z,
+                         int64_t N, int E, int K, int gw) {
+  extern __shared__ float gate_lds[];          // [groups][E] fp32, then int
+  const int groups = GATE_BLOCK / gw;
+  const int gl = threadIdx.x & (gw - 1);
+  const int gid = threadIdx.x / gw;
+  float* sp = gate_lds + (size_t)gid * E;
+  int* sc = reinterpret_cast<int*>(gate_lds + (size_t)groups * E) +
+            (size_t)gid * E;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int e = gl + gw * r;
+    if (e < E) {
+      sp[e] = 0.f;
+      sc[e] = 0;
+    }
+  }
+  float zacc = 0.f;                            // group-uniform
+  for (int64_t t = (int64_t)blockIdx.x * groups + gid; t < N;
+       t += (int64_t)gridDim.x * groups) {
+    const T* x = logits + t * E;
+    T* pr = probs + t * E;
+    float v[R];
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int e = gl + gw * r;
+      v[r] = e < E ? ld1(x + e) : -INFINITY;
+      m = fmaxf(m, v[r]);
+    }
+    m = group_max(m, gw);
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      v[r] = expf(v[r] - m);                   // 0 beyond E
+      s += v[r];
+    }
+    s = group_sum(s, gw);
+    const float l = m + logf(s);
+    u64 key[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int e = gl + gw * r;
+      key[r] = 0;
+      if (e < E) {
+        const float p = v[r] / s;
+        st1(pr + e, p);
+        sp[e] += p;
+        key[r] = topk_key(stored(pr, p), e);
+      }
+    }
+    zacc += l * l;
+    u64 prev = 0;
+    for (int k = 0; k < K; ++k) {
+      u64 best = 0;                            // every real key is > 0
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        if ((k == 0 || key[r] < prev) && key[r] > best) best = key[r];
+      best = group_max(best, gw);
+      prev = best;
+      const int e = best ? (int)(0xFFFFFFFFu - (u32)best) : 0;
+      if ((e & (gw - 1)) == gl && e < E) sc[e] += 1;
+      if (gl == 0) {
+        idx[t * K + k] = e;
+        w[t * K + k] = topk_key_value(best);
+      }
+    }
+    if (gl == 0) lse[t] = l;
+  }
+  gate_block_partials(gate_lds, groups, E, gid, gl == 0, zacc, part_p,
+                      part_c, part_z);
+}
+
+// E > GATE_REG_E: one wave per token, the row re-read per pass and round
+template <typename T>
+__global__ __launch_bounds__(GATE_BLOCK)
+void moe_gate_fwd_loop_kernel(const T* __restrict__ logits, T* probs,
+                              int64_t* __restrict__ idx,
+                              float* __restrict__ w, float* __restrict__ lse,
+                              float* __restrict__ part_p,
+                              int* __restrict__ part_c,
+                              float* __restrict__ part_z, int64_t N, int E,
+                              int K) {
+  extern __shared__ float gate_lds[];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  float* sp = gate_lds + (size_t)wid * E;
+  int* sc = reinterpret_cast<int*>(gate_lds + (size_t)GATE_WAVES * E) +
+            (size_t)wid * E;
+  for (int e = lane; e < E; e += WAVE) {
+    sp[e] = 0.f;
+    sc[e] = 0;
+  }
+  float zacc = 0.f;                            // wave-uniform
+  for (int64_t t = (int64_t)blockIdx.x * GATE_WAVES + wid; t < N;
+       t += (int64_t)gridDim.x * GATE_WAVES) {
+    const T* x = logits + t * E;
+    T* pr = probs + t * E;
+    float m = -INFINITY;
+    for (int e = lane; e < E; e += WAVE) m = fmaxf(m, ld1(x + e));
+    m = wave_max(m);
+    float s = 0.f;
+    for (int e = lane; e < E; e += WAVE) s += expf(ld1(x + e) - m);
+    s = wave_sum(s);
+    const float l = m + logf(s);
+    for (int e = lane; e < E; e += WAVE) {
+      const float p = expf(ld1(x + e) - m) / s;
+      st1(pr + e, p);
+      sp[e] += p;
+    }
+    zacc += l * l;
+    // a lane re-reads only the elements it stored itself
+    u64 prev = 0;
+    for (int k = 0; k < K; ++k) {
+      u64 best = 0;
+      for (int e = lane; e < E; e += WAVE) {
+        const u64 key = topk_key(ld1(pr + e), e);
+        if ((k == 0 || key < prev) && key > best) best = key;
+      }
+      best = group_max(best, WAVE);
+      prev = best;
+      const int e = best ? (int)(0xFFFFFFFFu - (u32)best) : 0;
+      if ((e & (WAVE - 1)) == lane && e < E) sc[e] += 1;
+      if (lane == 0) {
+        idx[t * K + k] = e;
+        w[t * K + k] = topk_key_value(best);
+      }
+    }
+    if (lane == 0) lse[t] = l;
+  }
+  gate_block_partials(gate_lds, GATE_WAVES, E, wid, lane == 0, zacc, part_p,
+                      part_c, part_z);
+}
+
+// psum[e] = sum_g part_p[g,e], cnt[e] = sum_g part_c[g,e]: a block owns 64
+// columns, wave i sums rows i, i+16, ... in order, wave 0 adds the sixteen.
+// A grid of one block (E <= 64) forms aux and z as well.
+constexpr int COLSUM_BLOCK = 1024;
+constexpr int COLSUM_WAVES = COLSUM_BLOCK / WAVE;
+
+__global__ __launch_bounds__(COLSUM_BLOCK)
+void moe_gate_colsum_kernel(const float* __restrict__ part_p,
+                            const int* __restrict__ part_c,
+                            const float* __restrict__ part_z,
+                            float* __restrict__ psum, int* __restrict__ cnt,
+                            float* __restrict__ aux, float* __restrict__ z,
+                            int G, int E, double aux_scale, double z_scale) {
+  __shared__ float sp[COLSUM_WAVES][WAVE];
+  __shared__ int sc[COLSUM_WAVES][WAVE];
+  __shared__ double red[16];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int e = blockIdx.x * WAVE + lane;
+  float ps = 0.f;
+  int cs = 0;
+  if (e < E) {
+#pragma unroll 4
+    for (int g = wid; g < G; g += COLSUM_WAVES) {
+      ps += part_p[(int64_t)g * E + e];
+      cs += part_c[(int64_t)g * E + e];
+    }
+  }
+  sp[wid][lane] = ps;
+  sc[wid][lane] = cs;
+  __syncthreads();
+  double a = 0.0;                              // aux, z: fp64, one rounding
+  if (wid == 0 && e < E) {
+#pragma unroll
+    for (int i = 1; i < COLSUM_WAVES; ++i) {
+      ps += sp[i][lane];
+      cs += sc[i][lane];
+    }
+    psum[e] = ps;
+    cnt[e] = cs;
+    a = (double)ps * (double)cs;
+  }
+  if (gridDim.x == 1) {                        // block-uniform
+    double zs = 0.0;
+    for (int g = threadIdx.x; g < G; g += COLSUM_BLOCK) zs += part_z[g];
+    a = block_sum_f64(a, red);
+    zs = block_sum_f64(zs, red);
+    if (threadIdx.x == 0) {
+      aux[0] = (float)(a * aux_scale);
+      z[0] = (float)(zs * z_scale);
+    }
+  }
+}
+
+// aux = aux_scale * sum_e psum[e]*cnt[e], z = z_scale * sum_g part_z[g]:
+// one block, strided per-thread fp64 sums, then a fixed-order block sum.
+__global__ __launch_bounds__(GATE_BLOCK)
+void moe_gate_scalars_kernel(const float* __restrict__ psum,
+                             const int* __restrict__ cnt,
+                             const float* __restrict__ part_z,
+                             float* __restrict__ aux, float* __restrict__ z,
+                             int G, int E, double aux_scale,
+                             double z_scale) {
+  __shared__ double red[16];
+  double a = 0.0, zs = 0.0;
+  for (int e = threadIdx.x; e < E; e += GATE_BLOCK)
+    a += (double)psum[e] * (double)cnt[e];
+  for (int g = threadIdx.x; g < G; g += GATE_BLOCK) zs += part_z[g];
+  a = block_sum_f64(a, red);
+  zs = block_sum_f64(zs, red);
+  if (threadIdx.x == 0) {
+    aux[0] = (float)(a * aux_scale);
+    z[0] = (float)(zs * z_scale);
+  }
+}
+
+// gate backward: gw lanes per token (a power of two, enough for one 16 B
+// access each up to a whole wave), p32 recomputed from logits and lse,
+//   dp = g_probs + g_aux * aux_scale * cnt
+//   dlogits = p32 * (dp - <p32, dp>) + g_z * z_scale * lse * p32
+// g_probs / g_aux / g_z may be null (zero); the scalars are read here.
+template <typename T, bool VECIO>
+__global__ __launch_bounds__(GATE_BLOCK)
+void moe_gate_grad_kernel(const T* __restrict__ g_probs,
+                          const float* __restrict__ g_aux,
+                          const float* __restrict__ g_z,
+                          const T* __restrict__ logits,
+                          const float* __restrict__ lse,
+                          const int* __restrict__ cnt,
+                          T* __restrict__ dlogits, int64_t N, int E,
+                          float aux_scale, float z_scale, int gw) {
+  constexpr int V = VECIO ? VecIO<T>::VEC : 1;
+  const int groups = GATE_BLOCK / gw;
+  const int gl = threadIdx.x & (gw - 1);
+  const int gid = threadIdx.x / gw;
+  const float ca = g_aux ? g_aux[0] * aux_scale : 0.f;
+  const float cz = g_z ? g_z[0] * z_scale : 0.f;
+  for (int64_t t = (int64_t)blockIdx.x * groups + gid; t < N;
+       t += (int64_t)gridDim.x * groups) {
+    const T* x = logits + t * E;
+    const T* gp = g_probs ? g_probs + t * E : nullptr;
+    T* dst = dlogits + t * E;
+    const float l = lse[t];
+    float dot = 0.f;
+    for (int i = gl * V; i < E; i += gw * V) {
+      float xv[V], gv[V];
+      if constexpr (VECIO) VecIO<T>::load(x + i, xv);
+      else xv[0] = ld1(x + i);
+#pragma unroll
+      for (int j = 0; j < V; ++j) gv[j] = 0.f;
+      if (gp) {
+        if constexpr (VECIO) VecIO<T>::load(gp + i, gv);
+        else gv[0] = ld1(gp + i);
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        dot += expf(xv[j] - l) * (gv[j] + ca * (float)cnt[i + j]);
+    }
+    dot = group_sum(dot, gw);
+    const float zl = cz * l;
+    for (int i = gl * V; i < E; i += gw * V) {
+      float xv[V], gv[V];
+      if constexpr (VECIO) VecIO<T>::load(x + i, xv);
+      else xv[0] = ld1(x + i);
+#pragma unroll
+      for (int j = 0; j < V; ++j) gv[j] = 0.f;
+      if (gp) {
+        if constexpr (VECIO) VecIO<T>::load(gp + i, gv);
+        else gv[0] = ld1(gp + i);
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float p = expf(xv[j] - l);
+        const float dp = gv[j] + ca * (float)cnt[i + j];
+        xv[j] = p * (dp - dot) + zl * p;
+      }
+      if constexpr (VECIO) VecIO<T>::store(dst + i, xv);
+      else st1(dst + i, xv[0]);
+    }
+  }
+}
+
 void check_routing(const torch::Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
               t.scalar_type() == at::kLong && t.dim() == 2,
@@ -610,4 +1004,158 @@ std::vector<torch::Tensor> moe_combine_rows_bwd(
     }
   });
   return {d_recv, dwk};
+}
+
+// the fused gate's grid cap and the tokens a block takes per pass: with
+// N > 2 * tokens_per_block(E) * max_blocks every block loops at least twice
+int64_t moe_gate_max_blocks() { return GATE_MAX_BLOCKS; }
+int64_t moe_gate_tokens_per_block(int64_t E) {
+  return E <= GATE_REG_E ? GATE_BLOCK / gate_group_width(E) : GATE_WAVES;
+}
+
+// logits [N, E] -> probs [N, E], idx [N, K] int64, w [N, K] fp32,
+// lse [N] fp32, psum [E] fp32, cnt [E] int32, aux [] fp32, z [] fp32
+std::vector<torch::Tensor> moe_gate_fwd(torch::Tensor logits, int64_t K) {
+  check_rows(logits, "logits");
+  const int64_t N = logits.size(0), E = logits.size(1);
+  check_k(K);
+  TORCH_CHECK(N >= 1, "moe_gate_fwd: no tokens");
+  TORCH_CHECK(K <= E, "moe_gate_fwd: K (", K, ") > E (", E, ")");
+  TORCH_CHECK(E <= MOE_MAX_E, "moe_gate_fwd: E (", E, ") > 2048");
+  const int gw = gate_group_width(E);
+  const int groups = (int)moe_gate_tokens_per_block(E);
+  const int G = (int)std::min<int64_t>((N + groups - 1) / groups,
+                                       GATE_MAX_BLOCKS);
+  auto probs = torch::empty_like(logits);
+  auto idx = torch::empty({N, K}, logits.options().dtype(at::kLong));
+  // the fp32 outputs share one allocation; the [G, E] workspace is apart,
+  // so a saved lse / aux does not keep it alive
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto i32 = logits.options().dtype(at::kInt);
+  auto fout = torch::empty({N * K + N + E + 2}, f32);
+  int64_t off = 0;
+  auto take = [&off](const torch::Tensor& buf, int64_t n) {
+    auto t = buf.narrow(0, off, n);
+    off += n;
+    return t;
+  };
+  auto w = take(fout, N * K).view({N, K});
+  auto lse = take(fout, N);
+  auto psum = take(fout, E);
+  auto aux = take(fout, 1).squeeze(0);
+  auto z = take(fout, 1).squeeze(0);
+  auto cnt = torch::empty({E}, i32);
+  auto fwork = torch::empty({(int64_t)G * E + G}, f32);
+  off = 0;
+  auto part_p = take(fwork, (int64_t)G * E);
+  auto part_z = take(fwork, G);
+  auto part_c = torch::empty({(int64_t)G * E}, i32);
+  const size_t lds = (size_t)groups * E * (sizeof(float) + sizeof(int));
+  auto stream = hetu_current_stream();
+#define GATE_FWD_ARGS                                                      \
+  (const scalar_t*)logits.data_ptr(), (scalar_t*)probs.data_ptr(),         \
+      idx.data_ptr<int64_t>(), w.data_ptr<float>(), lse.data_ptr<float>(), \
+      part_p.data_ptr<float>(), part_c.data_ptr<int>(),                    \
+      part_z.data_ptr<float>(), N, (int)E, (int)K
+  MOE_DISPATCH(logits, "moe_gate_fwd", [&] {
+    if (E <= WAVE) {
+      hipLaunchKernelGGL((moe_gate_fwd_kernel<scalar_t, 1>), dim3(G),
+                         dim3(GATE_BLOCK), lds, stream, GATE_FWD_ARGS, gw);
+    } else if (E <= 2 * WAVE) {
+      hipLaunchKernelGGL((moe_gate_fwd_kernel<scalar_t, 2>), dim3(G),
+                         dim3(GATE_BLOCK), lds, stream, GATE_FWD_ARGS, gw);
+    } else if (E <= GATE_REG_E) {
+      hipLaunchKernelGGL((moe_gate_fwd_kernel<scalar_t, GATE_REG_E / WAVE>),
+                         dim3(G), dim3(GATE_BLOCK), lds, stream,
+                         GATE_FWD_ARGS, gw);
+    } else {
+      hipLaunchKernelGGL((moe_gate_fwd_loop_kernel<scalar_t>), dim3(G),
+                         dim3(GATE_BLOCK), lds, stream, GATE_FWD_ARGS);
+    }
+  });
+#undef GATE_FWD_ARGS
+  HIP_CHECK(hipGetLastError());
+  const double n = (double)N;
+  const double aux_scale = (double)E / (n * n);
+  const double z_scale = 1.0 / n;
+  const int cgrid = (int)((E + WAVE - 1) / WAVE);
+  hipLaunchKernelGGL(moe_gate_colsum_kernel, dim3(cgrid), dim3(COLSUM_BLOCK),
+                     0, stream, part_p.data_ptr<float>(),
+                     part_c.data_ptr<int>(), part_z.data_ptr<float>(),
+                     psum.data_ptr<float>(), cnt.data_ptr<int>(),
+                     aux.data_ptr<float>(), z.data_ptr<float>(), G, (int)E,
+                     aux_scale, z_scale);
+  if (cgrid > 1)
+    hipLaunchKernelGGL(moe_gate_scalars_kernel, dim3(1), dim3(GATE_BLOCK), 0,
+                       stream, psum.data_ptr<float>(), cnt.data_ptr<int>(),
+                       part_z.data_ptr<float>(), aux.data_ptr<float>(),
+                       z.data_ptr<float>(), G, (int)E, aux_scale, z_scale);
+  return {probs, idx, w, lse, psum, cnt, aux, z};
+}
+
+// g_probs [N, E] | none, g_aux [] fp32 | none, g_z [] fp32 | none (device
+// scalars, read in the kernel), logits [N, E], lse [N] fp32, cnt [E] int32
+// -> dlogits [N, E]
+torch::Tensor moe_gate_grad(c10::optional<torch::Tensor> g_probs,
+                            c10::optional<torch::Tensor> g_aux,
+                            c10::optional<torch::Tensor> g_z,
+                            torch::Tensor logits, torch::Tensor lse,
+                            torch::Tensor cnt) {
+  check_rows(logits, "logits");
+  const int64_t N = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(N >= 1 && E >= 1, "moe_gate_grad: empty logits");
+  TORCH_CHECK(E <= MOE_MAX_E, "moe_gate_grad: E (", E, ") > 2048");
+  TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() &&
+              lse.scalar_type() == at::kFloat && lse.dim() == 1 &&
+              lse.size(0) == N, "moe_gate_grad: lse must be fp32 [N]");
+  TORCH_CHECK(cnt.is_cuda() && cnt.is_contiguous() &&
+              cnt.scalar_type() == at::kInt && cnt.dim() == 1 &&
+              cnt.size(0) == E, "moe_gate_grad: cnt must be int32 [E]");
+  const void* gp = nullptr;
+  if (g_probs.has_value()) {
+    check_rows(*g_probs, "g_probs");
+    TORCH_CHECK(g_probs->sizes() == logits.sizes() &&
+                g_probs->scalar_type() == logits.scalar_type(),
+                "moe_gate_grad: g_probs must match logits");
+    gp = g_probs->data_ptr();
+  }
+  auto scalar = [](const c10::optional<torch::Tensor>& t,
+                   const char* what) -> const float* {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                t->numel() == 1, "moe_gate_grad: ", what,
+                " must be one fp32 value on the GPU");
+    return t->data_ptr<float>();
+  };
+  const float* ga = scalar(g_aux, "g_aux");
+  const float* gz = scalar(g_z, "g_z");
+  auto dlogits = torch::empty_like(logits);
+  const double n = (double)N;
+  const float aux_scale = (float)((double)E / (n * n));
+  const float z_scale = (float)(2.0 / n);
+  auto stream = hetu_current_stream();
+  MOE_DISPATCH(logits, "moe_gate_grad", [&] {
+    const scalar_t* xp = (const scalar_t*)logits.data_ptr();
+    scalar_t* dp = (scalar_t*)dlogits.data_ptr();
+    const bool vec = gp ? can_vec<scalar_t>(E, {xp, dp, gp})
+                        : can_vec<scalar_t>(E, {xp, dp});
+    const int V = vec ? VecIO<scalar_t>::VEC : 1;
+    const int gw = gate_group_width((E + V - 1) / V);
+    const int groups = GATE_BLOCK / gw;
+    const int grid = row_grid((N + groups - 1) / groups);
+    if (vec) {
+      hipLaunchKernelGGL((moe_gate_grad_kernel<scalar_t, true>), dim3(grid),
+                         dim3(GATE_BLOCK), 0, stream, (const scalar_t*)gp,
+                         ga, gz, xp, lse.data_ptr<float>(),
+                         cnt.data_ptr<int>(), dp, N, (int)E, aux_scale,
+                         z_scale, gw);
+    } else {
+      hipLaunchKernelGGL((moe_gate_grad_kernel<scalar_t, false>), dim3(grid),
+                         dim3(GATE_BLOCK), 0, stream, (const scalar_t*)gp,
+                         ga, gz, xp, lse.data_ptr<float>(),
+                         cnt.data_ptr<int>(), dp, N, (int)E, aux_scale,
+                         z_scale, gw);
+    }
+  });
+  return dlogits;
 }
