@@ -3,9 +3,15 @@
 Reference context: Hetu's user-facing model stack is training-first; for
 serving parity this engine runs the same Llama/GPT weights with a
 fixed-capacity KV cache.  MI355X-native: prefill goes through the
-hand-written flash-attention kernel (one pass over the prompt), decode
-steps use cached K/V with a single fused read per layer; all norms /
-RoPE / SwiGLU hit the same HIP kernels as training via ops.functional.
+hand-written flash-attention kernel (one pass over the prompt).  A decode
+step (one new token) appends its K/V row to the cache and then calls
+F.flash_attn_decode on the whole layer cache and the current length: on
+the GPU (bf16, head dim 64 or 128) that is the split-KV HIP kernel, which
+reads each cached K and V row once per KV head, in place, with the length
+taken from an int32 device tensor that generate() advances in place; on
+the CPU, and for other dtypes or head dims, it is fp32 torch math on the
+visible slice of the cache.  All norms / RoPE / SwiGLU hit the same HIP
+kernels as training via ops.functional.
 
 Weights load from a hetu_amd checkpoint dir (utils/checkpoint format,
 incl. checkpoints converted from HF with utils/hf_convert) or from an
@@ -55,13 +61,21 @@ class LlamaKVCache:
         self.k = torch.zeros(shape, device=device, dtype=dtype)
         self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.len = 0
+        # rows of the cache a decode step attends, the new token's included
+        # (pos0 + 1), for the GPU decode kernel.  generate() advances it in
+        # place; whoever steps _forward by hand keeps it in step
+        # (kv_len.fill_(pos0 + 1)).
+        self.kv_len = torch.zeros(batch, device=device, dtype=torch.int32)
 
 
 class LlamaGenerator:
     def __init__(self, cfg: LlamaConfig, state: Dict[str, torch.Tensor],
                  device: Optional[torch.device] = None,
-                 dtype: torch.dtype = torch.float32):
+                 dtype: torch.dtype = torch.float32,
+                 decode_impl: Optional[str] = None):
         self.cfg = cfg
+        # forwarded to F.flash_attn_decode: None (auto), "torch" or "hip"
+        self.decode_impl = decode_impl
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() else "cpu")
         self.dtype = dtype
@@ -113,9 +127,19 @@ class LlamaGenerator:
         cache.v[layer][:, :, pos0:pos0 + S] = v.permute(0, 2, 1, 3)
         kk = cache.k[layer][:, :, :pos0 + S]
         vv = cache.v[layer][:, :, :pos0 + S]
+        if S == 1:
+            # the whole layer cache and the length: nothing is sliced, cast
+            # or repeated here
+            kc, vc = cache.k[layer], cache.v[layer]
+            on_hip = F.flash_attn_decode_on_hip(q[:, 0], kc, vc,
+                                                impl=self.decode_impl)
+            o, _ = F.flash_attn_decode(
+                q[:, 0], kc, vc, cache.kv_len if on_hip else pos0 + 1,
+                self.scale, impl=self.decode_impl)
+            return o.reshape(B, 1, H * dh) \
+                @ self.w[f"l{layer}.attn.wo.weight"].t()
         qt = q.permute(0, 2, 1, 3)
-        if S > 1 and qt.is_cuda and dh == 128 \
-                and qt.dtype == torch.bfloat16:
+        if qt.is_cuda and dh == 128 and qt.dtype == torch.bfloat16:
             o, _ = F.flash_attn_fwd(qt.contiguous(), kk.contiguous(),
                                     vv.contiguous(), True, self.scale)
         else:
@@ -167,6 +191,7 @@ class LlamaGenerator:
         cache = LlamaKVCache(self.cfg, B, S + max_new_tokens, self.device,
                              self.dtype)
         gen = torch.Generator(device="cpu").manual_seed(seed)
+        cache.kv_len.fill_(S)
         logits = self._forward(ids, cache, 0)
         pos = S
         out = [ids]
@@ -178,6 +203,7 @@ class LlamaGenerator:
                 alive &= (nxt.cpu() != eos_id)
                 if not alive.any():
                     break
+            cache.kv_len.add_(1)
             logits = self._forward(nxt.unsqueeze(1), cache, pos)
             pos += 1
         return torch.cat(out, dim=1)
@@ -189,8 +215,11 @@ class GPTGenerator:
 
     def __init__(self, cfg, state: Dict[str, torch.Tensor],
                  device: Optional[torch.device] = None,
-                 dtype: torch.dtype = torch.float32):
+                 dtype: torch.dtype = torch.float32,
+                 decode_impl: Optional[str] = None):
         self.cfg = cfg
+        # forwarded to F.flash_attn_decode: None (auto), "torch" or "hip"
+        self.decode_impl = decode_impl
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() else "cpu")
         self.dtype = dtype
@@ -202,21 +231,30 @@ class GPTGenerator:
         b = self.w.get(f"{name}.bias")
         return y + b if b is not None else y
 
-    def _attn(self, x, layer, kcache, vcache, pos0):
+    def _attn(self, x, layer, kcache, vcache, pos0, kv_len=None):
         cfg = self.cfg
         B, S, _ = x.shape
         H = cfg.n_head
         dh = cfg.hidden // H
         qkv = self._lin(x, f"h{layer}.attn.wqkv")
         q, k, v = qkv.chunk(3, -1)
+        q1 = q.view(B, S, H, dh)[:, 0]          # decode: a view into qkv
         q = q.view(B, S, H, dh).permute(0, 2, 1, 3)
         kcache[layer][:, :, pos0:pos0 + S] = \
             k.view(B, S, H, dh).permute(0, 2, 1, 3)
         vcache[layer][:, :, pos0:pos0 + S] = \
             v.view(B, S, H, dh).permute(0, 2, 1, 3)
+        if S == 1:
+            on_hip = kv_len is not None and F.flash_attn_decode_on_hip(
+                q1, kcache[layer], vcache[layer], impl=self.decode_impl)
+            o, _ = F.flash_attn_decode(
+                q1, kcache[layer], vcache[layer],
+                kv_len if on_hip else pos0 + 1, self.scale,
+                impl=self.decode_impl)
+            return self._lin(o.reshape(B, 1, H * dh), f"h{layer}.attn.wo")
         kk = kcache[layer][:, :, :pos0 + S]
         vv = vcache[layer][:, :, :pos0 + S]
-        if S > 1 and q.is_cuda and dh == 128 and q.dtype == torch.bfloat16:
+        if q.is_cuda and dh == 128 and q.dtype == torch.bfloat16:
             o, _ = F.flash_attn_fwd(q.contiguous(), kk.contiguous(),
                                     vv.contiguous(), True, self.scale)
         else:
@@ -230,7 +268,10 @@ class GPTGenerator:
         o = o.permute(0, 2, 1, 3).reshape(B, S, H * dh)
         return self._lin(o, f"h{layer}.attn.wo")
 
-    def _forward(self, ids, kcache, vcache, pos0):
+    def _forward(self, ids, kcache, vcache, pos0, kv_len=None):
+        """kv_len: int32 device tensor [B] holding pos0 + 1 for a decode
+        step on the GPU (generate() advances one in place); without it the
+        length is the Python int."""
         cfg = self.cfg
         S = ids.shape[1]
         pos = torch.arange(pos0, pos0 + S, device=self.device)
@@ -238,7 +279,7 @@ class GPTGenerator:
         for i in range(cfg.n_layer):
             h = F.layernorm_fwd(x, self.w[f"h{i}.ln1.weight"],
                                 self.w[f"h{i}.ln1.bias"], 1e-5)[0]
-            x = x + self._attn(h, i, kcache, vcache, pos0)
+            x = x + self._attn(h, i, kcache, vcache, pos0, kv_len)
             h = F.layernorm_fwd(x, self.w[f"h{i}.ln2.weight"],
                                 self.w[f"h{i}.ln2.bias"], 1e-5)[0]
             h = F.gelu_fwd(self._lin(h, f"h{i}.mlp.wfc"))
@@ -260,12 +301,14 @@ class GPTGenerator:
                          device=self.device, dtype=self.dtype)
         vc = torch.zeros_like(kc)
         gen = torch.Generator(device="cpu").manual_seed(seed)
-        logits = self._forward(ids, kc, vc, 0)
+        kv_len = torch.full((B,), S, dtype=torch.int32, device=self.device)
+        logits = self._forward(ids, kc, vc, 0, kv_len)
         out = [ids]
         pos = S
         for _ in range(max_new_tokens):
             nxt = sample_next(logits, temperature, top_k, top_p, gen)
             out.append(nxt.unsqueeze(1))
-            logits = self._forward(nxt.unsqueeze(1), kc, vc, pos)
+            kv_len.add_(1)
+            logits = self._forward(nxt.unsqueeze(1), kc, vc, pos, kv_len)
             pos += 1
         return torch.cat(out, dim=1)

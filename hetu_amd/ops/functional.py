@@ -548,6 +548,159 @@ def _attn_ref_bwd(dout, q, k, v, out, lse, causal, scale):
 
 
 # ---------------------------------------------------------------------------
+# Decode attention: one query token per sequence against a KV cache read in
+# place (ops/hip/attention_decode.hip; docs/KERNELS.md "Decode attention")
+# ---------------------------------------------------------------------------
+
+_DECODE_IMPLS = (None, "torch", "hip")
+
+
+def _decode_hip_ineligible(q, k_cache, v_cache, kv_len) -> Optional[str]:
+    """Why ops/hip/attention_decode.hip cannot take this input, or None."""
+    ts = (("q", q), ("k_cache", k_cache), ("v_cache", v_cache))
+    for name, t in ts:
+        if not t.is_cuda:
+            return f"{name} is not on the GPU"
+        if t.dtype != torch.bfloat16:
+            return f"{name} is {t.dtype}, not bf16"
+    if q.shape[-1] not in (64, 128):
+        return f"head dim {q.shape[-1]} is not 64 or 128"
+    if k_cache.shape[1] < 1 or q.shape[1] % k_cache.shape[1]:
+        return (f"H ({q.shape[1]}) is not a multiple of Hkv "
+                f"({k_cache.shape[1]})")
+    if isinstance(kv_len, torch.Tensor):
+        if not kv_len.is_cuda:
+            return "kv_len is a CPU tensor (pass an int or a device tensor)"
+        if kv_len.dtype != torch.int32:
+            return f"kv_len is {kv_len.dtype}, not int32"
+    for name, t in ts:
+        if t.stride(-1) != 1:
+            return f"{name} has a non-unit last stride"
+        # (the stride of a size-1 dim is never multiplied by anything)
+        if any(s % 8 for s, n in zip(t.stride()[:-1], t.shape) if n > 1) \
+                or t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned in every stride"
+    return None
+
+
+def _decode_auto_hip(B: int, Hkv: int, L: int) -> bool:
+    """Where the HIP kernel was ahead of the composition it replaces with
+    disjoint min-max ranges in scripts/bench_decode_attn.py
+    (profiles/r05_decode_attention.md, per-shape table): all 27 rows, bf16,
+    D = 128 at H/Hkv 32/32 and 32/8 and D = 64 at 16/16, B in {1, 16, 64},
+    kv_len in {512, 2048, 8192}, by 4.2-36x.  The smallest row (B = 1,
+    kv_len 512) is the kernel's floor of two launches, 12 us against the
+    composition's 73-85 us, so no corner goes to the torch branch.  A
+    further 18 rows at H/Hkv 32/4, 32/1 and 24/4 (section 3a there) win by
+    2.1-52x.  Shapes between and beyond the measured ones pass without
+    having been timed: that part is extrapolated."""
+    return True
+
+
+def _decode_check_shapes(q, k_cache, v_cache):
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 \
+            or k_cache.shape != v_cache.shape \
+            or k_cache.shape[0] != q.shape[0] \
+            or k_cache.shape[3] != q.shape[2]:
+        raise ValueError(
+            "flash_attn_decode: need q [B, H, D] and k_cache, v_cache "
+            f"[B, Hkv, L, D]; got {tuple(q.shape)}, {tuple(k_cache.shape)}, "
+            f"{tuple(v_cache.shape)}")
+
+
+def _decode_torch(q, k_cache, v_cache, kv_len, scale):
+    """fp32 math on the given inputs, one rounding to q's dtype.  An int
+    length slices the cache and repeats the KV heads, the composition the
+    generators ran before the kernel existed (bit-identical to it); a
+    tensor length masks, by selection: rows past kv_len[b] may hold
+    anything."""
+    B, H, D = q.shape
+    Hkv, L = k_cache.shape[1], k_cache.shape[2]
+    rep = H // Hkv
+    qt = q.unsqueeze(2)                                   # [B, H, 1, D]
+    if not isinstance(kv_len, torch.Tensor):
+        n = min(max(int(kv_len), 0), L)
+        kk = k_cache[:, :, :n]
+        vv = v_cache[:, :, :n]
+        kr = kk.repeat_interleave(rep, dim=1) if rep > 1 else kk
+        vr = vv.repeat_interleave(rep, dim=1) if rep > 1 else vv
+        scores = (qt.float() @ kr.float().transpose(-1, -2)) * scale
+        p = torch.softmax(scores, dim=-1)
+        o = (p @ vr.float()).to(q.dtype)
+        return o.squeeze(2), torch.logsumexp(scores, dim=-1).squeeze(-1)
+    n = kv_len.to(q.device).clamp(0, L).view(B, 1, 1)
+    valid = torch.arange(L, device=q.device).view(1, 1, L) < n   # [B, 1, L]
+    keep = valid.unsqueeze(-1)                                   # [B, 1, L, 1]
+    kf = torch.where(keep, k_cache.float(), 0.0)
+    vf = torch.where(keep, v_cache.float(), 0.0)
+    if rep > 1:
+        kf = kf.repeat_interleave(rep, dim=1)
+        vf = vf.repeat_interleave(rep, dim=1)
+    scores = (qt.float() @ kf.transpose(-1, -2)) * scale         # [B,H,1,L]
+    scores = scores.masked_fill(~valid.unsqueeze(1), float("-inf"))
+    lse = torch.logsumexp(scores, dim=-1)                        # [B, H, 1]
+    p = torch.where(valid.unsqueeze(1),
+                    torch.exp(scores - lse.unsqueeze(-1)), 0.0)
+    o = (p @ vf).to(q.dtype)
+    return o.squeeze(2), lse.squeeze(-1)
+
+
+def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None) -> bool:
+    """Whether flash_attn_decode sends this call to the HIP kernel (with
+    impl="hip" always: an ineligible input is then an error there).  The
+    generators ask before they choose between the device length tensor and
+    the Python int, which keeps the torch branch on its slicing form."""
+    if impl == "torch":
+        return False
+    if impl == "hip":
+        return True
+    return (_decode_hip_ineligible(q, k_cache, v_cache, kv_len) is None
+            and "fa" not in _TORCH_FB
+            and _decode_auto_hip(q.shape[0], k_cache.shape[1],
+                                 k_cache.shape[2]))
+
+
+def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
+                      num_splits: int = 0, impl=None):
+    """Attention of ONE new token per sequence over a KV cache.
+
+    q [B, H, D]; k_cache, v_cache [B, Hkv, L, D] (H % Hkv == 0), taken with
+    their strides: a layer slice of a [n_layer, B, Hkv, L, D] cache and a q
+    that is a view into a fused qkv output are read in place.  kv_len is an
+    int (every row attends keys 0 .. kv_len-1) or an int32 tensor [B]; it
+    is clamped to [0, L] and rows of the cache past it may hold anything.
+    Returns (out [B, H, D] in q's dtype, lse [B, H] fp32 = log sum_j
+    exp(scale * q.k_j), the definition flash_attn_fwd uses); kv_len == 0
+    gives out = 0, lse = -inf.
+
+    impl: "hip" = the split-KV kernel (bf16, D 64 or 128, GPU; an error on
+    anything else, never a fallback); "torch" = fp32 torch math; None = the
+    kernel where it is eligible and measured ahead, else torch.  num_splits
+    (HIP only): 0 lets the launcher choose from B, Hkv, L and the CU count
+    (never from the values of kv_len, so a captured graph stays valid);
+    >= 1 forces it."""
+    if impl not in _DECODE_IMPLS:
+        raise ValueError("flash_attn_decode: impl must be None, 'torch' or "
+                         f"'hip', got {impl!r}")
+    _decode_check_shapes(q, k_cache, v_cache)
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if not flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len, impl):
+        return _decode_torch(q, k_cache, v_cache, kv_len, scale)
+    why = _decode_hip_ineligible(q, k_cache, v_cache, kv_len)
+    if why is not None:
+        raise RuntimeError(f"flash_attn_decode(impl='hip'): {why}")
+    if not isinstance(kv_len, torch.Tensor):
+        # a fill kernel, not a host-to-device copy
+        n = min(max(int(kv_len), 0), k_cache.shape[2])
+        kv_len = torch.full((q.shape[0],), n, dtype=torch.int32,
+                            device=q.device)
+    out, lse = ext().flash_attn_decode(q, k_cache, v_cache, kv_len,
+                                       float(scale), int(num_splits))
+    return out, lse
+
+
+# ---------------------------------------------------------------------------
 # GEMM — hand-written MFMA bf16 kernel for the transformer hot path;
 # library (hipBLASLt via torch.matmul) for general shapes.
 # ---------------------------------------------------------------------------

@@ -163,6 +163,16 @@ torch::Tensor moe_gate_grad(c10::optional<torch::Tensor> g_probs,
                             c10::optional<torch::Tensor> g_z,
                             torch::Tensor logits, torch::Tensor lse,
                             torch::Tensor cnt);
+// attention_decode.hip
+int64_t decode_attn_tile();
+int64_t decode_attn_num_splits(int64_t B, int64_t Hkv, int64_t L,
+                               int64_t cus);
+std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
+                                             torch::Tensor k_cache,
+                                             torch::Tensor v_cache,
+                                             torch::Tensor kv_len,
+                                             double scale,
+                                             int64_t num_splits);
 
 // embed_cache.cpp
 void register_embed_cache(pybind11::module& m);
@@ -237,4 +247,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gate_tokens_per_block", &moe_gate_tokens_per_block);
   m.def("moe_gate_fwd", &moe_gate_fwd);
   m.def("moe_gate_grad", &moe_gate_grad);
+  m.def("decode_attn_tile", &decode_attn_tile);
+  m.def("decode_attn_num_splits", &decode_attn_num_splits);
+  m.def("flash_attn_decode", &flash_attn_decode, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
+        py::arg("scale"), py::arg("num_splits") = 0);
 }

@@ -32,6 +32,7 @@ SOURCES = [
     "attention_v2.hip",
     "attention_bwd_v3.hip",
     "attention_bwd_v2.hip",
+    "attention_decode.hip",
     "quant.hip",
     "moe.hip",
     "ltgemm.cpp",
