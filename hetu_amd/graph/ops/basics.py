@@ -910,6 +910,46 @@ def _deduce_matmul_ds(op, x: Tensor, w: Tensor, out: Tensor,
     out.device_group = x.device_group or w.device_group
 
 
+def _deduce_grad_w_ds(op, gy: Tensor, x: Tensor, out: Tensor):
+    """DS of dw = gy^T @ x (MatMulGradWOp, LinearGradWBOp output 0)."""
+    nd = gy.ndim
+    # ALL leading (token) dims of gy/x are the contraction; gy cols ->
+    # out dim 0; x cols -> out dim 1
+    _deduce_matmul_ds(op, gy, x, out,
+                      x_k_dims=list(range(nd - 1)),
+                      w_k_dims=list(range(x.ndim - 1)),
+                      x_pass={nd - 1: 0},
+                      w_pass={x.ndim - 1: 1})
+
+
+def _deduce_reduce_leading_ds(gy: Tensor, ref: Tensor, out: Tensor):
+    """DS of db = sum of gy over its leading dims (ReduceLeadingOp,
+    LinearGradWBOp output 1); ref is the bias."""
+    if gy.ds is not None:
+        n = gy.ds.device_num
+        table = []
+        ncol = gy.ds.get_dim(gy.ndim - 1)
+        # token splits become partial
+        npart = gy.ds.partial
+        for d in gy.ds.split_dims():
+            if d != gy.ndim - 1:
+                npart *= gy.ds.get_dim(d)
+        for i in range(n):
+            st = gy.ds.map_device_to_state_index(i)
+            ipart = st.get(-2, 0)
+            for d in gy.ds.split_dims():
+                if d != gy.ndim - 1:
+                    ipart = ipart * gy.ds.get_dim(d) + st.get(d, 0)
+            ent = {}
+            if ncol > 1:
+                ent[0] = st.get(gy.ndim - 1, 0)
+            if npart > 1:
+                ent[-2] = ipart
+            table.append(ent)
+        out.ds = ds_from_index_table(n, table, {0: ncol, -2: npart})
+    out.device_group = ref.device_group
+
+
 class LinearOp(OpInterface):
     """y = x @ W^T (+ b); W stored [out_features, in_features] (torch
     convention). inputs: x [..., K], w [N, K], optional bias [N]."""
@@ -942,14 +982,15 @@ class LinearOp(OpInterface):
         dx = _make(gr, MatMul2DOp(), [gy, w], {"trans_a": False,
                                                "trans_b": False},
                    name="linear_dx").output()
+        if len(op.inputs) > 2:
+            # dw and db from one op: the bias gradient's column sums ride
+            # the weight-gradient GEMM (F.linear_wgrad_bias)
+            wb = _make(gr, LinearGradWBOp(), [gy, x, op.inputs[2]],
+                       name="linear_dwb")
+            return [dx, wb.output(0), wb.output(1)]
         # dw = gy^T @ x  (flattened over leading dims)
         dw = _make(gr, MatMulGradWOp(), [gy, x], name="linear_dw").output()
-        grads = [dx, dw]
-        if len(op.inputs) > 2:
-            db = _make(gr, ReduceLeadingOp(), [gy, op.inputs[2]],
-                       name="linear_db").output()
-            grads.append(db)
-        return grads
+        return [dx, dw]
 
 
 class MatMul2DOp(OpInterface):
@@ -1038,14 +1079,7 @@ class MatMulGradWOp(OpInterface):
 
     def deduce_states(self, op):
         gy, x = op.inputs
-        nd = gy.ndim
-        # ALL leading (token) dims of gy/x are the contraction; gy cols ->
-        # out dim 0; x cols -> out dim 1
-        _deduce_matmul_ds(op, gy, x, op.outputs[0],
-                          x_k_dims=list(range(nd - 1)),
-                          w_k_dims=list(range(x.ndim - 1)),
-                          x_pass={nd - 1: 0},
-                          w_pass={x.ndim - 1: 1})
+        _deduce_grad_w_ds(op, gy, x, op.outputs[0])
 
     def compute(self, op, inputs, ctx):
         from ...ops import functional as F
@@ -1086,36 +1120,36 @@ class ReduceLeadingOp(OpInterface):
 
     def deduce_states(self, op):
         gy, ref = op.inputs
-        out = op.outputs[0]
-        if gy.ds is not None:
-            n = gy.ds.device_num
-            table = []
-            ncol = gy.ds.get_dim(gy.ndim - 1)
-            # token splits become partial
-            npart = gy.ds.partial
-            for d in gy.ds.split_dims():
-                if d != gy.ndim - 1:
-                    npart *= gy.ds.get_dim(d)
-            for i in range(n):
-                st = gy.ds.map_device_to_state_index(i)
-                ipart = st.get(-2, 0)
-                for d in gy.ds.split_dims():
-                    if d != gy.ndim - 1:
-                        ipart = ipart * gy.ds.get_dim(d) + st.get(d, 0)
-                ent = {}
-                if ncol > 1:
-                    ent[0] = st.get(gy.ndim - 1, 0)
-                if npart > 1:
-                    ent[-2] = ipart
-                table.append(ent)
-            out.ds = ds_from_index_table(n, table, {0: ncol, -2: npart})
-        out.device_group = ref.device_group
+        _deduce_reduce_leading_ds(gy, ref, op.outputs[0])
 
     def compute(self, op, inputs, ctx):
         from ...ops import functional as F
         gy = inputs[0]
         out = F.colsum(gy.reshape(-1, gy.shape[-1]))
         return [out.to(gy.dtype)]
+
+
+class LinearGradWBOp(OpInterface):
+    """Weight and bias gradient of a biased Linear in one op:
+    inputs gy [..., N], x [..., K], bias [N]; outputs dw [N, K] (what
+    MatMulGradWOp gives) and db [N] (what ReduceLeadingOp gives)."""
+    type = "LinearGradWB"
+
+    def infer_meta(self, attrs, inputs):
+        gy, x, b = inputs
+        return (MatMulGradWOp().infer_meta(attrs, [gy, x])
+                + ReduceLeadingOp().infer_meta(attrs, [gy, b]))
+
+    def deduce_states(self, op):
+        gy, x, b = op.inputs
+        _deduce_grad_w_ds(op, gy, x, op.outputs[0])
+        _deduce_reduce_leading_ds(gy, b, op.outputs[1])
+
+    def compute(self, op, inputs, ctx):
+        from ...ops import functional as F
+        gy, x = inputs[0], inputs[1]
+        dw, db = F.linear_wgrad_bias(gy, x)
+        return [dw, db]
 
 
 class BatchMatMulOp(OpInterface):

@@ -770,13 +770,20 @@ class FusedMLPGradOp(OpInterface):
         x2 = x.reshape(B * S, H)
         # dwproj = dy^T @ a; da->dgelu(+db1) fused; dwfc = dh^T @ x;
         # dx = dh @ wfc
-        dwproj = F.linear_wgrad(dy2, a).to(wproj.dtype)
+        db2 = None
+        if op.attrs.get("with_b2"):
+            # db2's column sums ride the dwproj GEMM where it is the hand
+            # kernel (F.linear_wgrad_bias), else colsum as before
+            dwproj, db2 = F.linear_wgrad_bias(dy2, a)
+            dwproj = dwproj.to(wproj.dtype)
+        else:
+            dwproj = F.linear_wgrad(dy2, a).to(wproj.dtype)
         dh, db1 = F.dgelu_bgrad(dy2, wproj, aux)
         dwfc = F.linear_wgrad(dh, x2).to(wfc.dtype)
         dx = F.linear_dgrad(dh, wfc).reshape(B, S, H)
         outs = [dx, dwfc, db1, dwproj]
-        if op.attrs.get("with_b2"):
-            outs.append(F.colsum(dy2).to(dy.dtype))
+        if db2 is not None:
+            outs.append(db2)
         return outs
 
 

@@ -329,6 +329,10 @@ def build_gpt_train_graph(cfg: GPTConfig, micro_batch: int, seq_len: int,
     g = graph or DefineAndRunGraph("gpt_train")
     if spec is None:
         spec = ParallelSpec(dp=dp, device_group=device_group)
+    if hetero is not None and any(p.tp > 1 for p in hetero.pipelines):
+        # a tp > 1 pipeline adds the row-parallel bias after its reduction;
+        # this one does the same so all pipelines round alike
+        spec = dataclasses.replace(spec, fuse_row_bias=False)
     push_graph(g)
     try:
         ds_in = spec.ds_activation(0)

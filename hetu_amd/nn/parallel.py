@@ -39,6 +39,10 @@ class ParallelSpec:
     cp: int = 1
     device_group: Optional[List[int]] = None
     sequence_parallel: bool = False
+    # RowParallelLinear at tp == 1 passes its bias into the Linear.  A
+    # hetero setup in which another pipeline runs tp > 1 turns this off so
+    # every pipeline rounds the bias add the same way (Linear, then Add).
+    fuse_row_bias: bool = True
 
     def __post_init__(self):
         if self.device_group is None:
@@ -226,6 +230,12 @@ class RowParallelLinear(Module):
 
     def forward(self, x):
         spec = self.spec
+        if spec.tp == 1 and not spec.sequence_parallel \
+                and spec.fuse_row_bias and self.bias is not None:
+            # no reduction between GEMM and bias: the bias rides the GEMM's
+            # epilogue and its gradient the weight-gradient GEMM
+            # (LinearOp.gradient), instead of an Add and a column sum
+            return ht.linear(x, self.weight, self.bias)
         y = ht.linear(x, self.weight)       # partial over tp
         if spec.tp > 1:
             dst = (spec.ds_activation_sp(0, 1) if spec.sequence_parallel

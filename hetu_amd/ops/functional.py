@@ -751,6 +751,48 @@ def _wgrad_auto_hip(T: int, N: int, K: int) -> bool:
     return tn % 8 == 0 and tk % 4 == 0 and (tn * tk) % 256 == 0 and T >= 2048
 
 
+_HETU_WGRAD_BIAS = os.environ.get("HETU_AMD_WGRAD_BIAS", "1")  # 1 | 0
+
+
+def _wgrad_bias_auto_fused(T: int, N: int, K: int, switch=None) -> bool:
+    """Whether linear_wgrad_bias(impl="auto") takes the fused kernel for an
+    eligible [T, N] x [T, K] input: exactly where _wgrad_auto_hip admits
+    the shape, unless HETU_AMD_WGRAD_BIAS=0 (then the unfused pair runs
+    everywhere, so both sides can be profiled from one tree).
+
+    scripts/bench_wgrad_bias.py (profiles/r06_wgrad_bias.md, per-shape
+    table) times fused against linear_wgrad + colsum on the four layer
+    shapes at T = 32768 and 8192, all of which _wgrad_auto_hip admits; the
+    table there states which rows are ahead with disjoint min-max ranges.
+    Shapes the wgrad rule admits but the script does not time (other
+    multiples of 256 tiles, T between the measured ones) pass untimed:
+    that part is extrapolated."""
+    switch = _HETU_WGRAD_BIAS if switch is None else switch
+    return str(switch) != "0" and _wgrad_auto_hip(T, N, K)
+
+
+class _DbRequest:
+    """linear_wgrad_bias asks linear_wgrad for the column sums of gy: the
+    hand-kernel routes fill `db` from the same launch, the library routes
+    leave it None."""
+    __slots__ = ("db",)
+
+    def __init__(self):
+        self.db = None
+
+
+# set only for the duration of linear_wgrad_bias's call of linear_wgrad,
+# which stays the one place that routes a weight-gradient GEMM
+_wgrad_db_request = None
+
+
+def _wgrad_hand_kernel(gy2, x2, req, fuse: bool):
+    if req is not None and fuse:
+        dw, req.db = ext().gemm_wgrad_bias_bf16(gy2, x2)
+        return dw
+    return ext().gemm_wgrad_bf16(gy2, x2)
+
+
 def linear_wgrad(gy, x, impl=None):
     """Weight gradient of y = x @ W^T: dW [N, K] = gy[..., N]^T @ x[..., K]
     over the flattened leading (token) dims.
@@ -759,6 +801,8 @@ def linear_wgrad(gy, x, impl=None):
     error if the input is not eligible (never a fallback); "auto" = the
     hand kernel where it measured faster, else the library.  None takes
     HETU_AMD_WGRAD (default auto)."""
+    global _wgrad_db_request
+    req, _wgrad_db_request = _wgrad_db_request, None
     impl = _HETU_WGRAD if impl is None else impl
     if impl not in _WGRAD_IMPLS:
         raise ValueError(f"linear_wgrad: impl must be one of {_WGRAD_IMPLS}, "
@@ -773,11 +817,42 @@ def linear_wgrad(gy, x, impl=None):
                 f"gy {tuple(gy2.shape)} {gy2.dtype} x {tuple(x2.shape)} "
                 f"{x2.dtype} contiguous={gy2.is_contiguous()},"
                 f"{x2.is_contiguous()} device={gy2.device}")
-        return ext().gemm_wgrad_bf16(gy2, x2)
+        return _wgrad_hand_kernel(gy2, x2, req, True)
     if (impl == "auto" and _gpu(gy2, x2) and _wgrad_hip_eligible(gy2, x2)
             and _wgrad_auto_hip(gy2.shape[0], gy2.shape[1], x2.shape[1])):
-        return ext().gemm_wgrad_bf16(gy2, x2)
+        return _wgrad_hand_kernel(
+            gy2, x2, req, _wgrad_bias_auto_fused(
+                gy2.shape[0], gy2.shape[1], x2.shape[1]))
     return torch.matmul(gy2.t(), x2)
+
+
+def linear_wgrad_bias(gy, x, impl=None):
+    """Weight and bias gradient of y = x @ W^T + b in one call:
+    (dW [N, K] = gy^T @ x, db [N] = sum over tokens of gy, in gy's dtype).
+
+    dW is linear_wgrad(gy, x, impl), so the routing rules are its rules and
+    live there.  Where that call runs the hand kernel it runs the bias
+    variant (ops/hip/gemm_wgrad.hip: the column sums ride the MFMA fragments
+    the GEMM already holds; dW comes out bit-identical) and db is a product
+    of the same launch; where it runs the library, db = colsum(gy).
+      impl "blas": torch.matmul + colsum.
+      impl "hip":  the fused kernel, an error if the input is not eligible
+                   (never a fallback).
+      impl "auto": the fused kernel exactly where _wgrad_auto_hip admits the
+                   shape (_wgrad_bias_auto_fused; HETU_AMD_WGRAD_BIAS=0
+                   turns the fusion off), else linear_wgrad + colsum, which
+                   is bit for bit what two separate ops compute.
+    None takes HETU_AMD_WGRAD (default auto)."""
+    global _wgrad_db_request
+    req = _DbRequest()
+    _wgrad_db_request = req
+    try:
+        dw = linear_wgrad(gy, x, impl)
+    finally:
+        _wgrad_db_request = None
+    if req.db is not None:
+        return dw, req.db
+    return dw, colsum(gy.reshape(-1, gy.shape[-1])).to(gy.dtype)
 
 
 _HETU_DGRAD = os.environ.get("HETU_AMD_DGRAD", "auto")  # auto|transposed|blas

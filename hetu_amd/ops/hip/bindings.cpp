@@ -94,6 +94,8 @@ void adam_step(torch::Tensor param32, torch::Tensor grad, torch::Tensor m,
 torch::Tensor gemm_bf16(torch::Tensor x, torch::Tensor w, bool trans_w);
 // gemm_wgrad.hip
 torch::Tensor gemm_wgrad_bf16(torch::Tensor gy, torch::Tensor x);
+std::vector<torch::Tensor> gemm_wgrad_bias_bf16(torch::Tensor gy,
+                                                torch::Tensor x);
 // transpose.hip
 torch::Tensor transpose2d(torch::Tensor w, c10::optional<torch::Tensor> out,
                           int64_t order);
@@ -217,6 +219,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("gemm_wgrad_bf16", &gemm_wgrad_bf16);
+  m.def("gemm_wgrad_bias_bf16", &gemm_wgrad_bias_bf16);
   m.def("transpose2d", &transpose2d, py::arg("w"),
         py::arg("out") = py::none(), py::arg("order") = 1);
   m.def("quantize_blockwise", &quantize_blockwise);

@@ -69,6 +69,23 @@
 // that are already dead ("pad, don't mask").  Every lane always holds a
 // valid address and EXEC is full throughout, which the tr reads require;
 // hence full tiles only.
+//
+// Bias variant (gemm_wgrad_bias_bf16_kernel)
+// ------------------------------------------
+// Also writes db[N] = sum_t gy[t, n], the bias gradient of the same Linear,
+// which is gy^T @ ones: one more MFMA per phase whose x operand is a
+// constant all-ones fragment.  Only the blocks with tk == 0 (one per tile
+// row tn after the remap) do it; the choice is ONE block-uniform branch at
+// the top of the kernel between two instantiations of the same body, so the
+// other blocks run the plain instantiation, with no test in the loop.  In phase
+// (S, H) the 4 waves of a wave row hold the same four gy fragments; wave wc
+// takes fragment wc, so every wave issues 17 MFMAs and no operand is read
+// twice.  To make that choice static the bias blocks keep their fragments
+// rotated by wc (wg_frag): fragment wc is always gf[0].  With
+// A = ones every row i of D[i][j] = sum_k A[i][k] gy[k][j] holds the 16
+// column sums, so lanes 0..15 of one accumulator register carry them: two
+// accumulators per wave (one per parity H), fp32 over all of T, rounded
+// once.  Each db element has exactly one writer: no atomics, no workspace.
 #include "attention_common.h"
 #include "ext_stream.h"
 
@@ -103,12 +120,31 @@ DEV void wg_stage(const bf16* src, int64_t ld, int tt, char* smem, int tid) {
   fa_glds16(p + 16 * ld, dst + 8192);
 }
 
+// which 16-column gy fragment of the wave row's 8 a wave keeps in slot m
+// (gf[m & 3] of parity m >> 2, acc[m][*]).  Plain blocks: fragment m.  Bias
+// blocks rotate each parity's four by the wave's column wc, so that slot 0
+// holds fragment wc, the one whose column sums wave wc owns; the rotation
+// costs nothing in the loop (it only permutes the read addresses, set up
+// once) and is undone by the epilogue's row offsets.  Every output element
+// still sums its K-steps in the same order: dW is bit-identical.
+template <bool BIAS>
+DEV int wg_frag(int m, int wc) {
+  return BIAS ? ((m & 4) | ((m + wc) & 3)) : m;
+}
+
+// all-ones bf16 MFMA operand (8 x 1.0)
+DEV bf16x8 wg_ones() {
+  const u32x2 v = {0x3F803F80u, 0x3F803F80u};
+  return fa_join(v, v);
+}
+
 // one phase: reads, one half-tile staged, 16 MFMA between two barriers
-template <int BUF, int P>
-DEV void wg_phase(f32x4 (&acc)[8][4], bf16x8 (&xf)[4],
+// (17 with BIAS: the column-sum MFMA, see the header)
+template <int BUF, int P, bool BIAS>
+DEV void wg_phase(f32x4 (&acc)[8][4], f32x4 (&bacc)[2], bf16x8 (&xf)[4],
                   const unsigned (&aaddr)[8], const unsigned (&baddr)[4],
                   const bf16* pA, const bf16* pB, int64_t ldA, int64_t ldB,
-                  int t, int nt, char* smem, int tid) {
+                  int t, int nt, char* smem, int tid, const bf16x8& ones) {
   constexpr int S = P >> 1, H = P & 1;
   constexpr int OFF = BUF * WG_IMG + S * WG_HALF;
   bf16x8 gf[4];
@@ -143,28 +179,35 @@ DEV void wg_phase(f32x4 (&acc)[8][4], bf16x8 (&xf)[4],
     for (int n = 0; n < 4; ++n)
       acc[4 * H + m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
           xf[n], gf[m], acc[4 * H + m][n], 0, 0, 0);
+  if constexpr (BIAS)
+    // column sums of this wave's share of the phase's gy fragments: the
+    // bias blocks read their fragments rotated by wc (wg_frag), so the
+    // share is always gf[0]
+    bacc[H] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, gf[0], bacc[H],
+                                                      0, 0, 0);
   __builtin_amdgcn_s_setprio(0);
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int BUF>
-DEV void wg_tile(f32x4 (&acc)[8][4], bf16x8 (&xf)[4],
+template <int BUF, bool BIAS>
+DEV void wg_tile(f32x4 (&acc)[8][4], f32x4 (&bacc)[2], bf16x8 (&xf)[4],
                  const unsigned (&aaddr)[8], const unsigned (&baddr)[4],
                  const bf16* pA, const bf16* pB, int64_t ldA, int64_t ldB,
-                 int t, int nt, char* smem, int tid) {
-  wg_phase<BUF, 0>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt, smem, tid);
-  wg_phase<BUF, 1>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt, smem, tid);
-  wg_phase<BUF, 2>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt, smem, tid);
-  wg_phase<BUF, 3>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt, smem, tid);
+                 int t, int nt, char* smem, int tid, const bf16x8& ones) {
+  wg_phase<BUF, 0, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt,
+                         smem, tid, ones);
+  wg_phase<BUF, 1, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt,
+                         smem, tid, ones);
+  wg_phase<BUF, 2, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt,
+                         smem, tid, ones);
+  wg_phase<BUF, 3, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt,
+                         smem, tid, ones);
 }
 
-__global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
-    const bf16* __restrict__ gy, const bf16* __restrict__ x,
-    bf16* __restrict__ dw, int T, int N, int K, int tiles_n, int tiles_k) {
-  __shared__ __attribute__((aligned(1024))) char smem[WG_LDS];
-
+// block id -> output tile (tn, tk)
+DEV void wg_remap(int tiles_n, int tiles_k, int& tn, int& tk) {
   // ---- XCD-aware bijective remap (T1) ----
   // blocks b, b+8, b+16.. share an XCD; give each XCD a contiguous chunk of
   // work ids, then fold every aligned run of 32 ids (what one XCD's 32 CUs
@@ -181,7 +224,6 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
   const int xcd = orig % 8, slot = orig / 8;
   const int wgid =
       (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-  int tn, tk;
   if (tiles_n % 8 == 0 && tiles_k % 4 == 0) {
     const int rect = wgid >> 5, in = wgid & 31;
     const int rects_k = tiles_k >> 2;
@@ -191,7 +233,14 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
     tn = wgid / tiles_k;
     tk = wgid % tiles_k;
   }
+}
 
+// the whole kernel for output tile (tn, tk); BIAS also writes this tile
+// row's 256 elements of db
+template <bool BIAS>
+DEV void wg_body(const bf16* __restrict__ gy, const bf16* __restrict__ x,
+                 bf16* __restrict__ dw, bf16* __restrict__ db, int T, int N,
+                 int K, int tn, int tk, char* smem) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid) >> 6;
@@ -216,7 +265,8 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
   unsigned aaddr[8], baddr[4];
 #pragma unroll
   for (int m = 0; m < 8; ++m)
-    aaddr[m] = lds0 + rowb + ((256 * wr + 32 * m + 8 * p) ^ (f << 5));
+    aaddr[m] = lds0 + rowb +
+               ((256 * wr + 32 * wg_frag<BIAS>(m, wc) + 8 * p) ^ (f << 5));
 #pragma unroll
   for (int n = 0; n < 4; ++n)
     baddr[n] = lds0 + WG_B_BASE + rowb +
@@ -227,6 +277,10 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
   for (int m = 0; m < 8; ++m)
 #pragma unroll
     for (int n = 0; n < 4; ++n) acc[m][n] = {0.f, 0.f, 0.f, 0.f};
+  // bias variant only (dead code otherwise): the column-sum accumulators,
+  // the all-ones x operand
+  f32x4 bacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  const bf16x8 ones = wg_ones();
   bf16x8 xf[4];
 
   // ---- prologue: tile 0 and k-step 0 of tile 1 ----
@@ -246,11 +300,14 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
 
   int t = 0;
   for (; t + 1 < nt; t += 2) {
-    wg_tile<0>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt, smem, tid);
-    wg_tile<1>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t + 1, nt, smem, tid);
+    wg_tile<0, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt,
+                     smem, tid, ones);
+    wg_tile<1, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t + 1, nt,
+                     smem, tid, ones);
   }
   if (t < nt)
-    wg_tile<0>(acc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt, smem, tid);
+    wg_tile<0, BIAS>(acc, bacc, xf, aaddr, baddr, pA, pB, ldA, ldB, t, nt,
+                     smem, tid, ones);
 
   // drain the (dead) tail loads before the workgroup's LDS can be released
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -267,8 +324,45 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
   for (int m = 0; m < 8; ++m)
 #pragma unroll
     for (int n = 0; n < 4; ++n)
-      fa_store4_bf16(dw + (row0 + 16 * m) * K + col0 + 16 * n,
+      fa_store4_bf16(dw + (row0 + 16 * wg_frag<BIAS>(m, wc)) * K + col0 +
+                         16 * n,
                      acc[m][n][0], acc[m][n][1], acc[m][n][2], acc[m][n][3]);
+  if constexpr (BIAS) {
+    // bacc[H][reg] = column sum of gy column 16 (4H + wc) + (lane & 15) of
+    // this wave row's half, the same in every row 4g + reg: lanes 0..15
+    // store register 0.  tn * 256 + 128 wr + 16 (4H + wc) + (lane & 15)
+    // < N by the full-tile precondition.
+    if (lane < 16) {
+      unsigned short* d = reinterpret_cast<unsigned short*>(db) +
+                          (int64_t)tn * WG_TILE_MN + 128 * wr + 16 * wc + lane;
+      const unsigned w = fa_cvt_pk(bacc[0][0], bacc[1][0]);
+      d[0] = (unsigned short)(w & 0xffffu);
+      d[64] = (unsigned short)(w >> 16);
+    }
+  }
+}
+
+__global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bf16_kernel(
+    const bf16* __restrict__ gy, const bf16* __restrict__ x,
+    bf16* __restrict__ dw, int T, int N, int K, int tiles_n, int tiles_k) {
+  __shared__ __attribute__((aligned(1024))) char smem[WG_LDS];
+  int tn, tk;
+  wg_remap(tiles_n, tiles_k, tn, tk);
+  wg_body<false>(gy, x, dw, nullptr, T, N, K, tn, tk, smem);
+}
+
+// the same, plus db[N] = column sums of gy, written by the tk == 0 blocks
+__global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bias_bf16_kernel(
+    const bf16* __restrict__ gy, const bf16* __restrict__ x,
+    bf16* __restrict__ dw, bf16* __restrict__ db, int T, int N, int K,
+    int tiles_n, int tiles_k) {
+  __shared__ __attribute__((aligned(1024))) char smem[WG_LDS];
+  int tn, tk;
+  wg_remap(tiles_n, tiles_k, tn, tk);
+  if (tk == 0)
+    wg_body<true>(gy, x, dw, db, T, N, K, tn, tk, smem);
+  else
+    wg_body<false>(gy, x, dw, db, T, N, K, tn, tk, smem);
 }
 
 // input check of the entry point; functional._wgrad_hip_eligible is the
@@ -302,4 +396,24 @@ torch::Tensor gemm_wgrad_bf16(torch::Tensor gy, torch::Tensor x) {
                      (const bf16*)gy.data_ptr(), (const bf16*)x.data_ptr(),
                      (bf16*)dw.data_ptr(), T, N, K, tiles_n, tiles_k);
   return dw;
+}
+
+// (dW[N, K] = gy^T @ x, db[N] = column sums of gy) from one launch
+std::vector<torch::Tensor> gemm_wgrad_bias_bf16(torch::Tensor gy,
+                                                torch::Tensor x) {
+  TORCH_CHECK(wg_eligible(gy, x),
+              "gemm_wgrad_bias_bf16 requires contiguous 2-D bf16 operands on "
+              "one GPU: "
+              "gy [T, N], x [T, K] with N % 256 == 0, K % 256 == 0 and "
+              "T % 64 == 0 (callers route everything else to the library)");
+  const int T = gy.size(0), N = gy.size(1), K = x.size(1);
+  auto dw = torch::empty({N, K}, x.options());
+  auto db = torch::empty({N}, gy.options());
+  const int tiles_n = N / WG_TILE_MN, tiles_k = K / WG_TILE_MN;
+  hipLaunchKernelGGL(gemm_wgrad_bias_bf16_kernel, dim3(tiles_n * tiles_k),
+                     dim3(WG_THREADS), 0, hetu_current_stream(),
+                     (const bf16*)gy.data_ptr(), (const bf16*)x.data_ptr(),
+                     (bf16*)dw.data_ptr(), (bf16*)db.data_ptr(), T, N, K,
+                     tiles_n, tiles_k);
+  return {dw, db};
 }
