@@ -38,7 +38,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
     const float* __restrict__ LSE, const float* __restrict__ DELTA,
     bf16* __restrict__ dQ, int B, int H, int Hkv, int S, int Skv,
     float scale, bool causal, FaStrides sq, FaStrides skv, FaStrides sdo,
-    FaStrides sdq, const int* __restrict__ cu, int lse_T) {
+    FaStrides sdq, const int* __restrict__ cu, int lse_T, bool mask_all) {
   static_assert(D == 128);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int b) -> char* { return smem + b * FA_KV_IMG; };
@@ -122,9 +122,12 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
     if (have_next) DQ_GLDS(k0 + 64, cur ^ 1);
 
     const bool active = !causal || (k0 <= wave_qmax + diag);
-    if (active)
-      FA_BWD_DQ_TILE(k_lds(cur), v_lds(cur), qreg, doreg, dq_acc, k0, my_q,
-                     S, Skv, diag, causal, lse_q, del_q, lane);
+    if (active) {
+      const bool boundary = fa_boundary_kv_tile(wave_qmax - 31, k0, S, Skv,
+                                                diag, causal, mask_all);
+      FA_BWD_DQ_TILE(boundary, k_lds(cur), v_lds(cur), qreg, doreg, dq_acc,
+                     k0, my_q, S, Skv, diag, causal, lse_q, del_q, lane);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
@@ -342,10 +345,12 @@ void fa2_bwd_kernels(const bf16* doutp, const bf16* qp, const bf16* kp,
                      bool causal, float scale, FaStrides sq, FaStrides skv,
                      FaStrides sdo, FaStrides sdq, FaStrides sdkv,
                      const int* cu, int lse_T, hipStream_t stream) {
+  const bool mask_all = fa_mask_all();
   hipLaunchKernelGGL((fa2_bwd_dq_kernel<128, VARLEN>),
                      dim3(B * H, (S + 255) / 256), dim3(THREADS), FA2_DQ_LDS,
                      stream, qp, kp, vp, doutp, lse, delta, dqp, B, H, Hkv,
-                     S, Skv, scale, causal, sq, skv, sdo, sdq, cu, lse_T);
+                     S, Skv, scale, causal, sq, skv, sdo, sdq, cu, lse_T,
+                     mask_all);
   hipLaunchKernelGGL((fa2_bwd_dkv_kernel<128, VARLEN>),
                      dim3(B * H, (Skv + 255) / 256), dim3(THREADS),
                      FA_DKV_LDS, stream, qp, kp, vp, doutp, lse, delta,

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_bwd_dq_kernel(
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ DELTA,
     bf16* __restrict__ dQ, int B, int H, int S, int Skv,
-    float scale, bool causal) {
+    float scale, bool causal, bool mask_all) {
   static_assert(D == 128);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int bb) -> char* { return smem + bb * FA_KV_IMG; };
@@ -123,14 +123,17 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_bwd_dq_kernel(
     const int k0 = t * 64;
     const int cur = t % NBUF;
     // B1: allow the newest tile's 4 loads to stay in flight
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    fa_wait_tile<4>(t + 1 >= n_tiles);
     __builtin_amdgcn_s_barrier();
     if (t + 2 < n_tiles) DQ3_ISSUE(k0 + 128, (t + 2) % NBUF);
 
     const bool active = !causal || (k0 <= wave_qmax + diag);
-    if (active)
-      FA_BWD_DQ_TILE(k_lds(cur), v_lds(cur), qreg, doreg, dq_acc, k0, my_q,
-                     S, Skv, diag, causal, lse_q, del_q, lane);
+    if (active) {
+      const bool boundary = fa_boundary_kv_tile(wave_qmax - 31, k0, S, Skv,
+                                                diag, causal, mask_all);
+      FA_BWD_DQ_TILE(boundary, k_lds(cur), v_lds(cur), qreg, doreg, dq_acc,
+                     k0, my_q, S, Skv, diag, causal, lse_q, del_q, lane);
+    }
   }
 #undef DQ3_ISSUE
 #undef DQ3_FAST
@@ -219,7 +222,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_bwd_dkv_kernel(
     const int cur = (t - t_start) & 1;
     // allow the newest issue's 2 loads to stay in flight; the V image
     // and tile t have landed once this retires
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    fa_wait_tile<2>(t + 1 >= n_q_tiles);
     __builtin_amdgcn_s_barrier();
 
     const bool active = !causal || (qt0 + 31 >= wave_kmin - diag);
@@ -265,13 +268,14 @@ std::vector<torch::Tensor> fa3_bwd_launch(
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
+  const bool mask_all = fa_mask_all();
   hipLaunchKernelGGL(fa3_bwd_dq_kernel<128>, dim3(B * H, (S + 255) / 256),
                      dim3(THREADS), FA3_DQ_LDS, stream,
                      (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
                      (const bf16*)v.data_ptr(), (const bf16*)dout.data_ptr(),
                      lse.data_ptr<float>(), delta.data_ptr<float>(),
                      (bf16*)dq.data_ptr(), B, H, S, Skv, (float)scale,
-                     causal);
+                     causal, mask_all);
   hipLaunchKernelGGL(fa3_bwd_dkv_kernel<128>,
                      dim3(B * H, (Skv + 255) / 256), dim3(THREADS),
                      FA_DKV_LDS, stream, (const bf16*)q.data_ptr(),

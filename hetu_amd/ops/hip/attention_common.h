@@ -9,6 +9,7 @@
 // the two backward kernels.  Each is validated by scripts/probe_fa2.hip.
 // All functions take lane / hi explicitly; nothing captures a local.
 #pragma once
+#include <cstdlib>
 #include <torch/extension.h>
 #include "common.h"
 
@@ -57,6 +58,17 @@ DEV void fa_glds16(const bf16* src, char* lds_dst) {
   __builtin_amdgcn_global_load_lds(
       (const __attribute__((address_space(1))) void*)src,
       (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+}
+
+// Loop-head wait of the counted-vmcnt pipelines: every load but the newest
+// tile's N has landed.  On the last tile nothing newer is in flight, so
+// the wait has to drain: a counted wait there returns while the tile's own
+// N loads are still outstanding, and the tile would be read before it
+// landed.
+template <int N>
+DEV void fa_wait_tile(bool last) {
+  if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N) : "memory");
 }
 
 // ds ops take a 32-bit LDS offset, not a generic 64-bit pointer
@@ -242,6 +254,31 @@ DEV int fa_first_q_tile(int kb0, int diag, bool causal) {
   return causal ? max(0, (kb0 - diag) / 32) : 0;
 }
 
+// A tile of the forward and dq kernels needs the masked stage only where it
+// crosses the key tail, the row tail or the causal diagonal of the wave's
+// 32 rows; everywhere else every select of the mask is false and the plain
+// stage computes the same bits without them.  Wave-uniform.  mask_all
+// (HETU_AMD_FA_MASK_ALL=1) forces the masked stage.  Rows qw0..qw0+31
+// against the 64-key tile at k0:
+DEV bool fa_boundary_kv_tile(int qw0, int k0, int S, int Skv, int diag,
+                             bool causal, bool mask_all) {
+  qw0 = __builtin_amdgcn_readfirstlane(qw0);    // the wave index is a VGPR
+  return mask_all || (k0 + 63 >= Skv) || (qw0 + 31 >= S) ||
+         (causal && k0 + 63 > qw0 + diag);
+}
+// The masked bodies.  In the C layout register r of a lane holds key
+// kbase + 4*hi + fa_crow(r) (+32 for a tile's second 32-key half).  The
+// three tests (key tail, row tail, causal diagonal) fold into one per-lane
+// bound, so an element costs a single compare against a constant:
+// masked iff 4*hi-relative key index > fa_mask_bound(kbase + 4*hi, ...).
+DEV constexpr int fa_crow(int r) { return (r & 3) + 8 * (r >> 2); }
+DEV int fa_mask_bound(int kbase_lane, int my_q, int S, int Skv, int diag,
+                      bool causal) {
+  int last = Skv - 1;                           // last key this row may see
+  if (causal) last = min(last, my_q + diag);
+  return (my_q >= S) ? -1 : last - kbase_lane;  // -1: every key masked
+}
+
 // ---- backward tile bodies (shared by the v2 and v3 kernels) ---------------
 // dq kernels, one 64-key tile: S^T = K Q_s^T and dP^T = V dO^T from the
 // row-major K / V images, dS rebuilt from the saved lse and packed
@@ -251,8 +288,23 @@ DEV int fa_first_q_tile(int kb0, int diag, bool causal) {
 // into 32 v_cndmask, and fa3_bwd_dq_kernel, which sits at its 256-VGPR
 // ceiling, then spills 88 B/lane to scratch; expanded in the kernel the
 // code compiles exactly as it did when each kernel carried its own copy.
-#define FA_BWD_DQ_TILE(k_img, v_img, qreg, doreg, dq_acc, k0, my_q, S, Skv, \
-                       diag, causal, lse_q, del_q, lane)                    \
+// `boundary` is wave-uniform (fa_boundary_kv_tile) and picks the dS stage;
+// the MFMA phases around it exist once (two whole copies of the tile spill).
+// The stage's two compile-time variants: the masked one, and the plain one
+// without key index, compare or select.
+#define FA_BWD_DQ_DS_MASKED(ds, sa, da, cbase, bound, lse_q, del_q)         \
+  _Pragma("unroll")                                                         \
+  for (int r = 0; r < 16; ++r) {                                            \
+    bool masked_ = (cbase) + fa_crow(r) > (bound);                          \
+    float pv_ = masked_ ? 0.f : __expf((sa)[r] - (lse_q));                  \
+    (ds)[r] = masked_ ? 0.f : pv_ * ((da)[r] - (del_q));                    \
+  }
+#define FA_BWD_DQ_DS_PLAIN(ds, sa, da, lse_q, del_q)                        \
+  _Pragma("unroll")                                                         \
+  for (int r = 0; r < 16; ++r)                                              \
+    (ds)[r] = __expf((sa)[r] - (lse_q)) * ((da)[r] - (del_q));
+#define FA_BWD_DQ_TILE(boundary, k_img, v_img, qreg, doreg, dq_acc, k0,     \
+                       my_q, S, Skv, diag, causal, lse_q, del_q, lane)      \
   do {                                                                      \
     const int iq_ = (lane) & 31;                                            \
     const int hi_ = (lane) >> 5;                                            \
@@ -272,13 +324,13 @@ DEV int fa_first_q_tile(int kb0, int diag, bool causal) {
         da_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf_, (doreg)[kk],     \
                                                       da_, 0, 0, 0);        \
       }                                                                     \
-      _Pragma("unroll")                                                     \
-      for (int r = 0; r < 16; ++r) {                                        \
-        int key_ = (k0) + 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * hi_;       \
-        bool masked_ = (key_ >= (Skv)) || ((my_q) >= (S)) ||                \
-                       ((causal) && key_ > (my_q) + (diag));                \
-        float pv_ = masked_ ? 0.f : __expf(sa_[r] - (lse_q));               \
-        ds_[ct][r] = masked_ ? 0.f : pv_ * (da_[r] - (del_q));              \
+      if (boundary) {                                                       \
+        const int bound_ = fa_mask_bound((k0) + 4 * hi_, my_q, S, Skv,      \
+                                         diag, causal);                     \
+        FA_BWD_DQ_DS_MASKED(ds_[ct], sa_, da_, 32 * ct, bound_, lse_q,      \
+                            del_q)                                          \
+      } else {                                                              \
+        FA_BWD_DQ_DS_PLAIN(ds_[ct], sa_, da_, lse_q, del_q)                 \
       }                                                                     \
     }                                                                       \
     _Pragma("unroll")                                                       \
@@ -297,6 +349,9 @@ DEV int fa_first_q_tile(int kb0, int diag, bool causal) {
 // S^T = K_s Q^T and dP^T = V dO^T, then P^T / dS^T round-trip through the
 // wave's two 72B-row images (p_img, then dS' right behind it) so tr_b16
 // can hand them back as A-fragments; dV += P^T dO, dK += dS^T Q.
+// Every tile takes the masked form: a mask-free stage for interior tiles
+// (as in the forward and dq) measured no faster here, the tile is bound by
+// its LDS traffic (profiles/r07_fa_tiles.md).
 DEV void fa_bwd_dkv_tile(const char* q_img, const char* do_img,
                          const char* vw_img, char* p_img,
                          const bf16x8 (&kreg)[8], f32x16 (&dk_acc)[4],
@@ -360,6 +415,13 @@ DEV void fa_bwd_dkv_tile(const char* q_img, const char* do_img,
           dstf, qa[dt], dk_acc[dt], 0, 0, 0);
     }
   }
+}
+
+// HETU_AMD_FA_MASK_ALL=1 runs the masked body on every tile (read at each
+// launch; for tests and for profiling both sides from one build)
+inline bool fa_mask_all() {
+  const char* e = std::getenv("HETU_AMD_FA_MASK_ALL");
+  return e != nullptr && e[0] == '1';
 }
 
 // ---- host launchers shared across the attention translation units --------

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
     const bf16* __restrict__ V, bf16* __restrict__ O,
     float* __restrict__ LSE, int B, int H, int Hkv, int S, int Skv,
     float scale, bool causal, FaStrides sq, FaStrides skv, FaStrides so,
-    const int* __restrict__ cu, int lse_T) {
+    const int* __restrict__ cu, int lse_T, bool mask_all) {
   static_assert(D == 128, "fa2 fwd: D=128 only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int b) -> char* { return smem + b * FA_KV_IMG; };
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
   for (int t = 0; t < n_tiles; ++t) {
     const int k0 = t * BN;
     const int cur = t % NBUF;
-    asm volatile("s_waitcnt vmcnt(%0)" :: "i"(2 * NGLDS) : "memory");
+    fa_wait_tile<2 * NGLDS>(t + 1 >= n_tiles);
     __builtin_amdgcn_s_barrier();
     if (t + 2 < n_tiles) ISSUE_GLDS(k0 + 2 * BN, (t + 2) % NBUF);
 
@@ -143,6 +143,48 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
     const bool active = !causal || (k0 <= wave_qmax + diag);
 
     float p[2][16];                // P^T rows: p[ct][r] = P[q][32ct+crow]
+    // mask + online softmax over p (all in-register; q = iq lane-local),
+    // returns the O rescale.  MASK=false (interior tiles, see
+    // fa_boundary_kv_tile) has no key index, no compare and no select
+    // around exp; only this stage exists twice, the MFMA phases once.
+    auto softmax = [&](auto mask_c) -> float {
+      constexpr bool MASK = decltype(mask_c)::value;
+      float pmax = -INFINITY;
+      int bound = 0;
+      if constexpr (MASK)
+        bound = fa_mask_bound(k0 + 4 * hi, my_q, S, Skv, diag, causal);
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if constexpr (MASK)
+            if (32 * ct + fa_crow(r) > bound) p[ct][r] = -INFINITY;
+          pmax = fmaxf(pmax, p[ct][r]);
+        }
+      pmax = fmaxf(pmax, __shfl_xor(pmax, 32, 64));
+      float mn = fmaxf(m_i, pmax);
+      float alpha = (m_i == -INFINITY || mn == -INFINITY)
+                        ? ((m_i == -INFINITY) ? 0.f : 1.f)
+                        : __expf(m_i - mn);
+      m_i = mn;
+      float psum = 0.f;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float pv;
+          if constexpr (MASK)
+            pv = (p[ct][r] == -INFINITY || mn == -INFINITY)
+                     ? 0.f : __expf(p[ct][r] - mn);
+          else
+            pv = __expf(p[ct][r] - mn);
+          p[ct][r] = pv;
+          psum += pv;
+        }
+      psum += __shfl_xor(psum, 32, 64);
+      l_i = l_i * alpha + psum;
+      return alpha;
+    };
     if (active) {
       // ---- S^T = K Q^T ------------------------------------------------
 #pragma unroll
@@ -162,36 +204,10 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
         for (int r = 0; r < 16; ++r) p[ct][r] = acc[r];
       }
 
-      // ---- mask + online softmax (all in-register; q = iq lane-local) --
-      float pmax = -INFINITY;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int key = k0 + 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          bool masked = (key >= Skv) || (my_q >= S) ||
-                        (causal && key > my_q + diag);
-          if (masked) p[ct][r] = -INFINITY;
-          pmax = fmaxf(pmax, p[ct][r]);
-        }
-      pmax = fmaxf(pmax, __shfl_xor(pmax, 32, 64));
-      float mn = fmaxf(m_i, pmax);
-      float alpha = (m_i == -INFINITY || mn == -INFINITY)
-                        ? ((m_i == -INFINITY) ? 0.f : 1.f)
-                        : __expf(m_i - mn);
-      m_i = mn;
-      float psum = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float pv = (p[ct][r] == -INFINITY || mn == -INFINITY)
-                         ? 0.f : __expf(p[ct][r] - mn);
-          p[ct][r] = pv;
-          psum += pv;
-        }
-      psum += __shfl_xor(psum, 32, 64);
-      l_i = l_i * alpha + psum;
+      const float alpha =
+          fa_boundary_kv_tile(wave_qmax - 31, k0, S, Skv, diag, causal,
+                              mask_all)
+              ? softmax(std::true_type{}) : softmax(std::false_type{});
       // rescale O^T
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
@@ -217,7 +233,6 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
               vf[dt], pfrag, o_acc[dt], 0, 0, 0);
       }
     }
-
   }
 
   // ---- epilogue -------------------------------------------------------
@@ -241,10 +256,11 @@ void fa2_fwd_launch(const bf16* q, const bf16* k, const bf16* v, bf16* o,
                     float scale, bool causal, FaStrides sq, FaStrides skv,
                     FaStrides so, const int* cu, int lse_T,
                     hipStream_t stream) {
+  const bool mask_all = fa_mask_all();
   dim3 grid(B * H, (S + BM - 1) / BM);
   hipLaunchKernelGGL(fa2_fwd_kernel<128>, grid, dim3(THREADS), FA_FWD_LDS,
                      stream, q, k, v, o, lse, B, H, Hkv, S, Skv, scale,
-                     causal, sq, skv, so, cu, lse_T);
+                     causal, sq, skv, so, cu, lse_T, mask_all);
 }
 
 // Packed-varlen entry (reference FlashAttention.cu mha_varlen_fwd): ONE
