@@ -241,6 +241,21 @@ def _norm_deduce(op):
         out.device_group = x.device_group
 
 
+def _norm_wgrad_ds(x):
+    """State of a norm's weight/bias grads given the activation x: partial
+    over the token-split dims (all but the last), duplicated over the
+    rest.  x must carry a state."""
+    n = x.ds.device_num
+    npart = x.ds.partial
+    for d in x.ds.split_dims():
+        if d != x.ndim - 1:
+            npart *= x.ds.get_dim(d)
+    states = {-2: npart} if npart > 1 else {}
+    if n // max(npart, 1) > 1:
+        states[-1] = n // max(npart, 1)
+    return DistributedStates(n, states)
+
+
 class LayerNormOp(OpInterface):
     type = "LayerNorm"
 
@@ -277,21 +292,9 @@ class LayerNormGradOp(OpInterface):
 
     def deduce_states(self, op):
         op.outputs[0].ds = op.inputs[1].ds
-        # dw/db over token-split input are partial
         x = op.inputs[1]
-        w = op.inputs[2]
         if x.ds is not None:
-            n = x.ds.device_num
-            npart = x.ds.partial
-            for d in x.ds.split_dims():
-                if d != x.ndim - 1:
-                    npart *= x.ds.get_dim(d)
-            states = {-2: npart} if npart > 1 else {}
-            if n // max(npart, 1) > 1:
-                states[-1] = n // max(npart, 1)
-            ds = DistributedStates(n, states)
-            op.outputs[1].ds = ds
-            op.outputs[2].ds = ds
+            op.outputs[1].ds = op.outputs[2].ds = _norm_wgrad_ds(x)
         for o in op.outputs:
             o.device_group = x.device_group
 
@@ -336,15 +339,7 @@ class RMSNormGradOp(OpInterface):
         op.outputs[0].ds = op.inputs[1].ds
         x = op.inputs[1]
         if x.ds is not None:
-            n = x.ds.device_num
-            npart = x.ds.partial
-            for d in x.ds.split_dims():
-                if d != x.ndim - 1:
-                    npart *= x.ds.get_dim(d)
-            states = {-2: npart} if npart > 1 else {}
-            if n // max(npart, 1) > 1:
-                states[-1] = n // max(npart, 1)
-            op.outputs[1].ds = DistributedStates(n, states)
+            op.outputs[1].ds = _norm_wgrad_ds(x)
         for o in op.outputs:
             o.device_group = x.device_group
 
@@ -846,19 +841,7 @@ class FusedAddLNGradOp(OpInterface):
         s = op.inputs[1]
         op.outputs[0].ds = s.ds
         if s.ds is not None:
-            n = s.ds.device_num
-            npart = s.ds.partial
-            for d in s.ds.split_dims():
-                if d != s.ndim - 1:
-                    npart *= s.ds.get_dim(d)
-            states = {}
-            if npart > 1:
-                states[-2] = npart
-            if n // max(npart, 1) > 1:
-                states[-1] = n // max(npart, 1)
-            wds = DistributedStates(n, states)
-            op.outputs[1].ds = wds
-            op.outputs[2].ds = wds
+            op.outputs[1].ds = op.outputs[2].ds = _norm_wgrad_ds(s)
         for out in op.outputs:
             out.device_group = s.device_group
 
@@ -920,17 +903,7 @@ class FusedAddRMSGradOp(OpInterface):
         s = op.inputs[1]
         op.outputs[0].ds = s.ds
         if s.ds is not None:
-            n = s.ds.device_num
-            npart = s.ds.partial
-            for d in s.ds.split_dims():
-                if d != s.ndim - 1:
-                    npart *= s.ds.get_dim(d)
-            states = {}
-            if npart > 1:
-                states[-2] = npart
-            if n // max(npart, 1) > 1:
-                states[-1] = n // max(npart, 1)
-            op.outputs[1].ds = DistributedStates(n, states)
+            op.outputs[1].ds = _norm_wgrad_ds(s)
         for out in op.outputs:
             out.device_group = s.device_group
 

@@ -21,8 +21,6 @@ import torch
 
 _EXT = None
 _EXT_ERR = None
-# norm backward variant: split dx + column-reduce dw/db kernels
-_NORM_V2 = os.environ.get("HETU_AMD_NORM_V2", "1") == "1"
 
 
 def _load_ext():
@@ -84,15 +82,38 @@ _FA_IMPL = 1 if os.environ.get("HETU_AMD_FA1", "")[:1] == "1" else 0
 
 
 # ---------------------------------------------------------------------------
-# RMSNorm (fused fwd/bwd; reference RMSNorm.cu — block per row)
+# RMSNorm / LayerNorm, plain and with the fused residual add (reference
+# RMSNorm.cu, FusedLayerNorm.cu:455-760).  On GPU all eight go through the
+# extension's two entry points, norm_fwd and norm_bwd.
 # ---------------------------------------------------------------------------
+
+def _opt(t, dtype=None):
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if dtype is None else t.to(dtype)
+
+
+def _norm_fwd_hip(x, resid, w, b, eps):
+    """LayerNorm when b is given, else RMSNorm; s = x + resid is normed and
+    returned when resid is given.  Returns (y, [s,] [mean,] rstd)."""
+    return tuple(ext().norm_fwd(x.contiguous(), _opt(resid),
+                                _opt(w, x.dtype), _opt(b, x.dtype), eps))
+
+
+def _norm_bwd_hip(dy, x, w, mean, rstd, dresid=None):
+    """LayerNorm when mean is given; dresid is added into dx.
+    Returns (dx, dw, [db])."""
+    return tuple(ext().norm_bwd(dy.contiguous(), x.contiguous(),
+                                _opt(w, x.dtype), _opt(mean),
+                                rstd.contiguous(), _opt(dresid)))
+
 
 def rmsnorm_fwd(x: torch.Tensor, w: torch.Tensor, eps: float
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """returns (y, rstd[rows] fp32)"""
     if _use_hip("rms", x):
-        return ext().rmsnorm_fwd(x.contiguous(),
-                                 w.contiguous().to(x.dtype), eps)
+        return _norm_fwd_hip(x, None, w, None, eps)
     xf = x.float()
     rstd = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
     y = (xf * rstd) * w.float()
@@ -102,13 +123,7 @@ def rmsnorm_fwd(x: torch.Tensor, w: torch.Tensor, eps: float
 def rmsnorm_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
                 rstd: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     if _use_hip("rms", x):
-        if _NORM_V2:
-            return ext().rmsnorm_bwd2(dy.contiguous(), x.contiguous(),
-                                      w.contiguous().to(x.dtype),
-                                      rstd.contiguous())
-        return ext().rmsnorm_bwd(dy.contiguous(), x.contiguous(),
-                                 w.contiguous().to(x.dtype),
-                                 rstd.contiguous())
+        return _norm_bwd_hip(dy, x, w, None, rstd)
     xf, dyf, wf = x.float(), dy.float(), w.float()
     r = rstd.unsqueeze(-1)
     xhat = xf * r
@@ -119,15 +134,10 @@ def rmsnorm_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     return dx.to(x.dtype), dw.to(w.dtype)
 
 
-# ---------------------------------------------------------------------------
-# LayerNorm (fused, Welford; reference FusedLayerNorm.cu:455-760)
-# ---------------------------------------------------------------------------
-
 def layernorm_fwd(x, w, b, eps):
+    """returns (y, mean[rows] fp32, rstd[rows] fp32)"""
     if _use_hip("ln", x):
-        return ext().layernorm_fwd(x.contiguous(),
-                                   w.contiguous().to(x.dtype),
-                                   b.contiguous().to(x.dtype), eps)
+        return _norm_fwd_hip(x, None, w, b, eps)
     xf = x.float()
     mean = xf.mean(-1, keepdim=True)
     var = xf.var(-1, unbiased=False, keepdim=True)
@@ -138,14 +148,7 @@ def layernorm_fwd(x, w, b, eps):
 
 def layernorm_bwd(dy, x, w, mean, rstd):
     if _use_hip("ln", x):
-        if _NORM_V2:
-            return ext().layernorm_bwd2(dy.contiguous(), x.contiguous(),
-                                        w.contiguous().to(x.dtype),
-                                        mean.contiguous(),
-                                        rstd.contiguous())
-        return ext().layernorm_bwd(dy.contiguous(), x.contiguous(),
-                                   w.contiguous().to(x.dtype),
-                                   mean.contiguous(), rstd.contiguous())
+        return _norm_bwd_hip(dy, x, w, mean, rstd)
     xf, dyf, wf = x.float(), dy.float(), w.float()
     mu = mean.unsqueeze(-1)
     r = rstd.unsqueeze(-1)
@@ -160,29 +163,21 @@ def layernorm_bwd(dy, x, w, mean, rstd):
     return dx.to(x.dtype), dw.to(w.dtype), db.to(w.dtype)
 
 
-# ---------------------------------------------------------------------------
-# SwiGLU: y = silu(x1) * x2 over last-dim halves (reference SwiGLU.cu:14,30)
-# ---------------------------------------------------------------------------
-
 def rmsnorm_fwd_res(x, resid, w, eps):
     """Fused residual-add + RMSNorm: s = x + resid; y = RMS(s).
     Returns (y, s, rstd)."""
     if _use_hip("rms", x):
-        return tuple(ext().rmsnorm_fwd_res(
-            x.contiguous(), resid.contiguous(),
-            w.contiguous().to(x.dtype), eps))
+        return _norm_fwd_hip(x, resid, w, None, eps)
     s = x + resid
     y, rstd = rmsnorm_fwd(s, w, eps)
     return y, s, rstd
 
 
 def rmsnorm_bwd_res(dy, s, w, rstd, ds_ext=None):
+    """returns (dsum = dRMS/ds (+ ds_ext), dw); dsum is the grad of both
+    add inputs."""
     if _use_hip("rms", s):
-        empty = torch.empty(0, dtype=s.dtype, device=s.device)
-        return tuple(ext().rmsnorm_bwd2_res(
-            dy.contiguous(), s.contiguous(), w.contiguous().to(s.dtype),
-            rstd.contiguous(),
-            ds_ext.contiguous() if ds_ext is not None else empty))
+        return _norm_bwd_hip(dy, s, w, None, rstd, ds_ext)
     dx, dw = rmsnorm_bwd(dy, s, w, rstd)
     if ds_ext is not None:
         dx = dx + ds_ext
@@ -193,9 +188,7 @@ def layernorm_fwd_res(x, resid, w, b, eps):
     """Fused residual-add + LayerNorm: s = x + resid; y = LN(s).
     Returns (y, s, mean, rstd)."""
     if _use_hip("ln", x):
-        return tuple(ext().layernorm_fwd_res(
-            x.contiguous(), resid.contiguous(),
-            w.contiguous().to(x.dtype), b.contiguous().to(x.dtype), eps))
+        return _norm_fwd_hip(x, resid, w, b, eps)
     s = x + resid
     y, mean, rstd = layernorm_fwd(s, w, b, eps)
     return y, s, mean, rstd
@@ -205,16 +198,16 @@ def layernorm_bwd_res(dy, s, w, mean, rstd, ds_ext=None):
     """returns (dsum = dLN/ds (+ ds_ext), dw, db); dsum is the grad of
     both add inputs."""
     if _use_hip("ln", s):
-        empty = torch.empty(0, dtype=s.dtype, device=s.device)
-        return tuple(ext().layernorm_bwd2_res(
-            dy.contiguous(), s.contiguous(), w.contiguous().to(s.dtype),
-            mean.contiguous(), rstd.contiguous(),
-            ds_ext.contiguous() if ds_ext is not None else empty))
+        return _norm_bwd_hip(dy, s, w, mean, rstd, ds_ext)
     dx, dw, db = layernorm_bwd(dy, s, w, mean, rstd)
     if ds_ext is not None:
         dx = dx + ds_ext
     return dx, dw, db
 
+
+# ---------------------------------------------------------------------------
+# SwiGLU: y = silu(x1) * x2 over last-dim halves (reference SwiGLU.cu:14,30)
+# ---------------------------------------------------------------------------
 
 def swiglu_fwd(x):
     if _use_hip("swiglu", x):

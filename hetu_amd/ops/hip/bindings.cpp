@@ -4,15 +4,16 @@
 #include <vector>
 
 // norms.hip
-std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
-                                       double eps);
-std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                       torch::Tensor w, torch::Tensor rstd);
-std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
-                                         torch::Tensor b, double eps);
-std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                         torch::Tensor w, torch::Tensor mean,
-                                         torch::Tensor rstd);
+std::vector<torch::Tensor> norm_fwd(torch::Tensor x,
+                                    c10::optional<torch::Tensor> resid,
+                                    torch::Tensor w,
+                                    c10::optional<torch::Tensor> b,
+                                    double eps);
+std::vector<torch::Tensor> norm_bwd(torch::Tensor dy, torch::Tensor x,
+                                    torch::Tensor w,
+                                    c10::optional<torch::Tensor> mean,
+                                    torch::Tensor rstd,
+                                    c10::optional<torch::Tensor> dresid);
 // reduce.hip
 torch::Tensor colsum(torch::Tensor x);
 // ltgemm.cpp
@@ -60,31 +61,6 @@ torch::Tensor dropout_bwd(torch::Tensor dy, torch::Tensor mask, double p,
 torch::Tensor embedding_fwd(torch::Tensor table, torch::Tensor ids);
 torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor ids,
                             int64_t num_rows);
-std::vector<torch::Tensor> rmsnorm_fwd_res(torch::Tensor x,
-                                           torch::Tensor resid,
-                                           torch::Tensor w, double eps);
-std::vector<torch::Tensor> rmsnorm_bwd2_res(torch::Tensor dy,
-                                            torch::Tensor s,
-                                            torch::Tensor w,
-                                            torch::Tensor rstd,
-                                            torch::Tensor ds_ext);
-std::vector<torch::Tensor> layernorm_fwd_res(torch::Tensor x,
-                                             torch::Tensor resid,
-                                             torch::Tensor w,
-                                             torch::Tensor b, double eps);
-std::vector<torch::Tensor> layernorm_bwd2_res(torch::Tensor dy,
-                                              torch::Tensor s,
-                                              torch::Tensor w,
-                                              torch::Tensor mean,
-                                              torch::Tensor rstd,
-                                              torch::Tensor ds_ext);
-std::vector<torch::Tensor> layernorm_bwd2(torch::Tensor dy, torch::Tensor x,
-                                          torch::Tensor w,
-                                          torch::Tensor mean,
-                                          torch::Tensor rstd);
-std::vector<torch::Tensor> rmsnorm_bwd2(torch::Tensor dy, torch::Tensor x,
-                                        torch::Tensor w,
-                                        torch::Tensor rstd);
 // adam.hip
 void adam_step(torch::Tensor param32, torch::Tensor grad, torch::Tensor m,
                torch::Tensor v, double lr, double beta1, double beta2,
@@ -184,16 +160,8 @@ void register_dataloader(pybind11::module& m);
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_embed_cache(m);
   register_dataloader(m);
-  m.def("rmsnorm_fwd", &rmsnorm_fwd);
-  m.def("rmsnorm_bwd", &rmsnorm_bwd);
-  m.def("layernorm_fwd", &layernorm_fwd);
-  m.def("layernorm_bwd", &layernorm_bwd);
-  m.def("layernorm_bwd2", &layernorm_bwd2);
-  m.def("layernorm_fwd_res", &layernorm_fwd_res);
-  m.def("rmsnorm_fwd_res", &rmsnorm_fwd_res);
-  m.def("rmsnorm_bwd2_res", &rmsnorm_bwd2_res);
-  m.def("layernorm_bwd2_res", &layernorm_bwd2_res);
-  m.def("rmsnorm_bwd2", &rmsnorm_bwd2);
+  m.def("norm_fwd", &norm_fwd);
+  m.def("norm_bwd", &norm_bwd);
   m.def("colsum", &colsum);
   m.def("lt_linear_gelu_aux", &lt_linear_gelu_aux);
   m.def("lt_dgelu_bgrad", &lt_dgelu_bgrad);

@@ -1,11 +1,23 @@
-// Fused RMSNorm / LayerNorm forward+backward for gfx950.
+// RMSNorm / LayerNorm forward and backward for gfx950, with the optional
+// fused residual add of the transformer pre-norm chain.
 //
-// Design (MI355X): one 256-thread block per row (grid-stride over rows),
-// wave64 shuffle reductions, bf16 loads vectorized as ushort8 (16 B/lane —
-// scalar bf16 loads halve HBM throughput on CDNA4). fp32 stats; dw/db
-// accumulated per-block in registers then one atomicAdd per element.
+// Three kernels, all memory-bound, all on 16 B/lane vector I/O (VecIO:
+// 8 bf16 or 4 fp32) with fp32 arithmetic and fp32 row statistics:
+//   norm_fwd_kernel<T, LN, RES>   one 256-thread block per row (grid-stride),
+//                                 block reductions for the row statistics
+//   norm_bwd_dx_kernel<T, LN>     one wave per row, shuffle reductions only,
+//                                 no LDS and no atomics
+//   norm_bwd_dwdb_kernel<T, LN>   column sums over a [rows_chunk x 512-col]
+//                                 tile per block, combined across row blocks
+//                                 by one fp32 atomicAdd per column
+// LN compiles in the mean and the bias; without it the kernels are RMSNorm.
+// Two host entry points, norm_fwd and norm_bwd, pick the instantiation from
+// which optional tensors are present and share one argument check.
 // Capability parity: reference RMSNorm.cu / FusedLayerNorm.cu:455-760.
 #include <torch/extension.h>
+
+#include <climits>
+
 #include "ext_stream.h"
 #include "common.h"
 
@@ -13,126 +25,19 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-// ---------------- RMSNorm ----------------
-
-template <typename T, bool RES>
-__global__ void rmsnorm_fwd_kernel(const T* __restrict__ x,
-                                   const T* __restrict__ resid,
-                                   const T* __restrict__ w,
-                                   T* __restrict__ y,
-                                   T* __restrict__ sum_out,
-                                   float* __restrict__ rstd_out,
-                                   int64_t rows, int D, float eps) {
-  constexpr int V = VecIO<T>::VEC;
-  __shared__ float smem[16];
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
-    const T* xr = x + row * D;
-    const T* rr = RES ? resid + row * D : nullptr;
-    T* yr = y + row * D;
-    T* sr = RES ? sum_out + row * D : nullptr;
-    float ss = 0.f;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V) {
-      float v[VecIO<T>::VEC];
-      VecIO<T>::load(xr + i, v);
-      if (RES) {
-        float rv[VecIO<T>::VEC];
-        VecIO<T>::load(rr + i, rv);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[j] += rv[j];
-        VecIO<T>::store(sr + i, v);
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j) ss += v[j] * v[j];
-    }
-    ss = block_sum(ss, smem);
-    float rstd = rsqrtf(ss / D + eps);
-    if (threadIdx.x == 0) rstd_out[row] = rstd;
-    const T* sum_r = RES ? sr : xr;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V) {
-      float v[VecIO<T>::VEC], wv[VecIO<T>::VEC];
-      VecIO<T>::load(sum_r + i, v);
-      VecIO<T>::load(w + i, wv);
-#pragma unroll
-      for (int j = 0; j < V; ++j) v[j] = v[j] * rstd * wv[j];
-      VecIO<T>::store(yr + i, v);
-    }
-  }
-}
-
-// dw accumulated per-thread in registers across this block's rows; ONE
-// atomicAdd per element per block at the end (grid is capped so total
-// atomic traffic is ~grid*D, not rows*D).
-template <typename T, int NCHUNK>
-__global__ void rmsnorm_bwd_kernel(const T* __restrict__ dy,
-                                   const T* __restrict__ x,
-                                   const T* __restrict__ w,
-                                   const float* __restrict__ rstd,
-                                   T* __restrict__ dx,
-                                   float* __restrict__ dw_accum,
-                                   int64_t rows, int D) {
-  constexpr int V = VecIO<T>::VEC;
-  __shared__ float smem[16];
-  float dwacc[NCHUNK][V];
-#pragma unroll
-  for (int c = 0; c < NCHUNK; ++c)
-#pragma unroll
-    for (int j = 0; j < V; ++j) dwacc[c][j] = 0.f;
-
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
-    const T* dyr = dy + row * D;
-    const T* xr = x + row * D;
-    T* dxr = dx + row * D;
-    const float r = rstd[row];
-    float dot = 0.f;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V) {
-      float dv[VecIO<T>::VEC], xv[VecIO<T>::VEC], wv[VecIO<T>::VEC];
-      VecIO<T>::load(dyr + i, dv);
-      VecIO<T>::load(xr + i, xv);
-      VecIO<T>::load(w + i, wv);
-#pragma unroll
-      for (int j = 0; j < V; ++j) dot += dv[j] * wv[j] * xv[j] * r;
-    }
-    dot = block_sum(dot, smem) / D;
-    int c = 0;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V, ++c) {
-      float dv[VecIO<T>::VEC], xv[VecIO<T>::VEC], wv[VecIO<T>::VEC];
-      VecIO<T>::load(dyr + i, dv);
-      VecIO<T>::load(xr + i, xv);
-      VecIO<T>::load(w + i, wv);
-      float o[VecIO<T>::VEC];
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float xhat = xv[j] * r;
-        o[j] = (dv[j] * wv[j] - xhat * dot) * r;
-        dwacc[c][j] += dv[j] * xhat;
-      }
-      VecIO<T>::store(dxr + i, o);
-    }
-  }
-  {
-    int c = 0;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V, ++c)
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        atomicAdd(dw_accum + i + j, dwacc[c][j]);
-  }
-}
-
-// ---------------- LayerNorm ----------------
-
 // RES: fuse the transformer residual add into the norm — loads x+resid,
 // writes the sum (feeds the next residual) alongside y, killing the
 // standalone elementwise add kernel (the at::native tail).
-template <typename T, bool RES>
-__global__ void layernorm_fwd_kernel(const T* __restrict__ x,
-                                     const T* __restrict__ resid,
-                                     const T* __restrict__ w,
-                                     const T* __restrict__ b,
-                                     T* __restrict__ y,
-                                     T* __restrict__ sum_out,
-                                     float* __restrict__ mean_out,
-                                     float* __restrict__ rstd_out,
-                                     int64_t rows, int D, float eps) {
+template <typename T, bool LN, bool RES>
+__global__ void norm_fwd_kernel(const T* __restrict__ x,
+                                const T* __restrict__ resid,
+                                const T* __restrict__ w,
+                                const T* __restrict__ b,
+                                T* __restrict__ y,
+                                T* __restrict__ sum_out,
+                                float* __restrict__ mean_out,
+                                float* __restrict__ rstd_out,
+                                int64_t rows, int D, float eps) {
   constexpr int V = VecIO<T>::VEC;
   __shared__ float smem[16];
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
@@ -152,230 +57,42 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
         VecIO<T>::store(sr + i, v);
       }
 #pragma unroll
-      for (int j = 0; j < V; ++j) { s += v[j]; ss += v[j] * v[j]; }
+      for (int j = 0; j < V; ++j) {
+        if (LN) s += v[j];
+        ss += v[j] * v[j];
+      }
     }
-    s = block_sum(s, smem);
-    ss = block_sum(ss, smem);
-    float mu = s / D;
-    float var = ss / D - mu * mu;
-    float rstd = rsqrtf(var + eps);
-    if (threadIdx.x == 0) { mean_out[row] = mu; rstd_out[row] = rstd; }
+    float mu = 0.f, rstd;
+    if (LN) {
+      s = block_sum(s, smem);
+      ss = block_sum(ss, smem);
+      mu = s / D;
+      float var = ss / D - mu * mu;
+      rstd = rsqrtf(var + eps);
+      if (threadIdx.x == 0) { mean_out[row] = mu; rstd_out[row] = rstd; }
+    } else {
+      ss = block_sum(ss, smem);
+      rstd = rsqrtf(ss / D + eps);
+      if (threadIdx.x == 0) rstd_out[row] = rstd;
+    }
     const T* sum_r = RES ? sr : xr;
     for (int i = threadIdx.x * V; i < D; i += BLOCK * V) {
       float v[VecIO<T>::VEC], wv[VecIO<T>::VEC], bv[VecIO<T>::VEC];
       VecIO<T>::load(sum_r + i, v);
       VecIO<T>::load(w + i, wv);
-      VecIO<T>::load(b + i, bv);
+      if (LN) VecIO<T>::load(b + i, bv);
 #pragma unroll
       for (int j = 0; j < V; ++j)
-        v[j] = (v[j] - mu) * rstd * wv[j] + bv[j];
+        v[j] = LN ? (v[j] - mu) * rstd * wv[j] + bv[j]
+                  : v[j] * rstd * wv[j];
       VecIO<T>::store(yr + i, v);
     }
   }
 }
 
-template <typename T, int NCHUNK>
-__global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
-                                     const T* __restrict__ x,
-                                     const T* __restrict__ w,
-                                     const float* __restrict__ mean,
-                                     const float* __restrict__ rstd,
-                                     T* __restrict__ dx,
-                                     float* __restrict__ dw_accum,
-                                     float* __restrict__ db_accum,
-                                     int64_t rows, int D) {
-  constexpr int V = VecIO<T>::VEC;
-  __shared__ float smem[16];
-  float dwacc[NCHUNK][V], dbacc[NCHUNK][V];
-#pragma unroll
-  for (int c = 0; c < NCHUNK; ++c)
-#pragma unroll
-    for (int j = 0; j < V; ++j) { dwacc[c][j] = 0.f; dbacc[c][j] = 0.f; }
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
-    const T* dyr = dy + row * D;
-    const T* xr = x + row * D;
-    T* dxr = dx + row * D;
-    const float mu = mean[row], r = rstd[row];
-    float c1 = 0.f, c2 = 0.f;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V) {
-      float dv[VecIO<T>::VEC], xv[VecIO<T>::VEC], wv[VecIO<T>::VEC];
-      VecIO<T>::load(dyr + i, dv);
-      VecIO<T>::load(xr + i, xv);
-      VecIO<T>::load(w + i, wv);
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float xhat = (xv[j] - mu) * r;
-        float wdy = dv[j] * wv[j];
-        c1 += wdy;
-        c2 += wdy * xhat;
-      }
-    }
-    c1 = block_sum(c1, smem) / D;
-    c2 = block_sum(c2, smem) / D;
-    int c = 0;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V, ++c) {
-      float dv[VecIO<T>::VEC], xv[VecIO<T>::VEC], wv[VecIO<T>::VEC];
-      VecIO<T>::load(dyr + i, dv);
-      VecIO<T>::load(xr + i, xv);
-      VecIO<T>::load(w + i, wv);
-      float o[VecIO<T>::VEC];
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float xhat = (xv[j] - mu) * r;
-        float wdy = dv[j] * wv[j];
-        o[j] = (wdy - c1 - xhat * c2) * r;
-        dwacc[c][j] += dv[j] * xhat;
-        dbacc[c][j] += dv[j];
-      }
-      VecIO<T>::store(dxr + i, o);
-    }
-  }
-  {
-    int c = 0;
-    for (int i = threadIdx.x * V; i < D; i += BLOCK * V, ++c)
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        atomicAdd(dw_accum + i + j, dwacc[c][j]);
-        atomicAdd(db_accum + i + j, dbacc[c][j]);
-      }
-  }
-}
-
-inline int row_grid(int64_t rows) {
-  // >> 256 workgroups to fill 256 CUs / 8 XCDs; cap and grid-stride
-  int64_t g = rows < 8192 ? rows : 8192;
-  return (int)(g > 0 ? g : 1);
-}
-
-}  // namespace
-
-std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
-                                       double eps) {
-  const int D = x.size(-1);
-  const int64_t rows = x.numel() / D;
-  TORCH_CHECK(D % 8 == 0, "rmsnorm: D must be a multiple of 8");
-  TORCH_CHECK(w.scalar_type() == x.scalar_type(),
-              "rmsnorm: w dtype must match x");
-  auto y = torch::empty_like(x);
-  auto rstd = torch::empty({rows}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  DISPATCH_FLOAT(x, "rmsnorm_fwd", [&] {
-    hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, false>),
-                       dim3(row_grid(rows)), dim3(BLOCK), 0, stream,
-                       (const scalar_t*)x.data_ptr(),
-                       (const scalar_t*)nullptr,
-                       (const scalar_t*)w.data_ptr(),
-                       (scalar_t*)y.data_ptr(), (scalar_t*)nullptr,
-                       rstd.data_ptr<float>(), rows, D, (float)eps);
-  });
-  return {y, rstd.view(at::IntArrayRef(x.sizes().begin(), x.sizes().end() - 1))};
-}
-
-std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                       torch::Tensor w, torch::Tensor rstd) {
-  const int D = x.size(-1);
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              dy.scalar_type() == x.scalar_type(),
-              "rmsnorm_bwd: dy/w dtype must match x");
-  const int64_t rows = x.numel() / D;
-  auto dx = torch::empty_like(x);
-  auto dw32 = torch::zeros({D}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  int grid = (int)std::min<int64_t>(rows, 1024);
-  DISPATCH_FLOAT(x, "rmsnorm_bwd", [&] {
-    constexpr int V = VecIO<scalar_t>::VEC;
-    const int nchunk = (D + BLOCK * V - 1) / (BLOCK * V);
-    auto launch = [&](auto tag) {
-      constexpr int NC = decltype(tag)::value;
-      hipLaunchKernelGGL((rmsnorm_bwd_kernel<scalar_t, NC>), dim3(grid),
-                         dim3(BLOCK), 0, stream,
-                         (const scalar_t*)dy.data_ptr(),
-                         (const scalar_t*)x.data_ptr(),
-                         (const scalar_t*)w.data_ptr(),
-                         rstd.data_ptr<float>(),
-                         (scalar_t*)dx.data_ptr(), dw32.data_ptr<float>(),
-                         rows, D);
-    };
-    if (nchunk <= 1) launch(std::integral_constant<int, 1>{});
-    else if (nchunk <= 2) launch(std::integral_constant<int, 2>{});
-    else if (nchunk <= 4) launch(std::integral_constant<int, 4>{});
-    else if (nchunk <= 8) launch(std::integral_constant<int, 8>{});
-    else TORCH_CHECK(false, "rmsnorm_bwd: D too large");
-  });
-  return {dx, dw32.to(w.scalar_type())};
-}
-
-std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
-                                         torch::Tensor b, double eps) {
-  const int D = x.size(-1);
-  const int64_t rows = x.numel() / D;
-  TORCH_CHECK(D % 8 == 0, "layernorm: D must be a multiple of 8");
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              b.scalar_type() == x.scalar_type(),
-              "layernorm: w/b dtype must match x");
-  auto y = torch::empty_like(x);
-  auto mean = torch::empty({rows}, x.options().dtype(at::kFloat));
-  auto rstd = torch::empty({rows}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  DISPATCH_FLOAT(x, "layernorm_fwd", [&] {
-    hipLaunchKernelGGL((layernorm_fwd_kernel<scalar_t, false>),
-                       dim3(row_grid(rows)), dim3(BLOCK), 0, stream,
-                       (const scalar_t*)x.data_ptr(),
-                       (const scalar_t*)nullptr,
-                       (const scalar_t*)w.data_ptr(),
-                       (const scalar_t*)b.data_ptr(),
-                       (scalar_t*)y.data_ptr(), (scalar_t*)nullptr,
-                       mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), rows, D, (float)eps);
-  });
-  auto row_sizes = at::IntArrayRef(x.sizes().begin(), x.sizes().end() - 1);
-  return {y, mean.view(row_sizes), rstd.view(row_sizes)};
-}
-
-std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                         torch::Tensor w, torch::Tensor mean,
-                                         torch::Tensor rstd) {
-  const int D = x.size(-1);
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              dy.scalar_type() == x.scalar_type(),
-              "layernorm_bwd: dy/w dtype must match x");
-  const int64_t rows = x.numel() / D;
-  auto dx = torch::empty_like(x);
-  auto dw32 = torch::zeros({D}, x.options().dtype(at::kFloat));
-  auto db32 = torch::zeros({D}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  int grid = (int)std::min<int64_t>(rows, 1024);
-  DISPATCH_FLOAT(x, "layernorm_bwd", [&] {
-    constexpr int V = VecIO<scalar_t>::VEC;
-    const int nchunk = (D + BLOCK * V - 1) / (BLOCK * V);
-    auto launch = [&](auto tag) {
-      constexpr int NC = decltype(tag)::value;
-      hipLaunchKernelGGL((layernorm_bwd_kernel<scalar_t, NC>), dim3(grid),
-                         dim3(BLOCK), 0, stream,
-                         (const scalar_t*)dy.data_ptr(),
-                         (const scalar_t*)x.data_ptr(),
-                         (const scalar_t*)w.data_ptr(),
-                         mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                         (scalar_t*)dx.data_ptr(), dw32.data_ptr<float>(),
-                         db32.data_ptr<float>(), rows, D);
-    };
-    if (nchunk <= 1) launch(std::integral_constant<int, 1>{});
-    else if (nchunk <= 2) launch(std::integral_constant<int, 2>{});
-    else if (nchunk <= 4) launch(std::integral_constant<int, 4>{});
-    else if (nchunk <= 8) launch(std::integral_constant<int, 8>{});
-    else TORCH_CHECK(false, "layernorm_bwd: D too large");
-  });
-  return {dx, dw32.to(w.scalar_type()), db32.to(w.scalar_type())};
-}
-
-// ---------------------------------------------------------------------------
-// v2 backward: split dx (wave-per-row, shuffle reductions, no atomics)
-// from dw/db (column-tile reduction kernel).  The fused block-per-row
-// version above is grid-capped at 1024 blocks by its dw atomic flush and
-// measured 5.7x off the bandwidth bound at the 7B shape.
-// ---------------------------------------------------------------------------
-namespace {
-
+// dx: a wave owns a row, so both row reductions are shuffles.  With dresid
+// the residual-grad accumulation is fused in (the adjoint of add+norm):
+// dx = dnorm/dsum + dresid, no standalone add kernel in the backward.
 template <typename T, bool LN>
 __global__ void norm_bwd_dx_kernel(const T* __restrict__ dy,
                                    const T* __restrict__ x,
@@ -424,8 +141,6 @@ __global__ void norm_bwd_dx_kernel(const T* __restrict__ dy,
         o[j] = LN ? (wdy - c1 - xhat * c2) * r : (wdy - xhat * c2) * r;
       }
       if (dresid != nullptr) {
-        // fused residual-grad accumulation (the adjoint of add+LN):
-        // dx = dLN/dsum + dresid, no standalone add kernel in backward
         float rv[VecIO<T>::VEC];
         VecIO<T>::load(dresid + row * D + i, rv);
 #pragma unroll
@@ -436,7 +151,7 @@ __global__ void norm_bwd_dx_kernel(const T* __restrict__ dy,
   }
 }
 
-// dw/db: column sums of dy*xhat / dy over a [ROWS_CHUNK x 512-col] tile
+// dw/db: column sums of dy*xhat / dy over a [rows_chunk x 512-col] tile
 // per block; each thread owns 2 adjacent columns (one dword load per row
 // per tensor), one atomicAdd pair per column at the end.
 template <typename T, bool LN>
@@ -479,17 +194,23 @@ __global__ void norm_bwd_dwdb_kernel(const T* __restrict__ dy,
   }
 }
 
-inline int v2_grid(int64_t rows) {
+inline int row_grid(int64_t rows) {
+  // >> 256 workgroups to fill 256 CUs / 8 XCDs; cap and grid-stride
+  int64_t g = rows < 8192 ? rows : 8192;
+  return (int)(g > 0 ? g : 1);
+}
+
+inline int dx_grid(int64_t rows) {
   int64_t g = (rows + 3) / 4;
   return (int)std::min<int64_t>(std::max<int64_t>(g, 1), 8192);
 }
 
 template <typename T, bool LN>
-void norm_bwd_v2_launch(const T* dy, const T* x, const T* w,
-                        const float* mean, const float* rstd, T* dx,
-                        float* dw, float* db, int64_t rows, int D,
-                        hipStream_t stream, const T* dresid = nullptr) {
-  hipLaunchKernelGGL((norm_bwd_dx_kernel<T, LN>), dim3(v2_grid(rows)),
+void norm_bwd_launch(const T* dy, const T* x, const T* w,
+                     const float* mean, const float* rstd, const T* dresid,
+                     T* dx, float* dw, float* db, int64_t rows, int D,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL((norm_bwd_dx_kernel<T, LN>), dim3(dx_grid(rows)),
                      dim3(256), 0, stream, dy, x, w, mean, rstd,
                      dresid, dx, rows, D);
   // pick rows_chunk so the grid lands around ~2048 blocks
@@ -502,172 +223,153 @@ void norm_bwd_v2_launch(const T* dy, const T* x, const T* w,
                      dy, x, mean, rstd, dw, db, rows, D, rows_chunk);
 }
 
+// ---- host side -----------------------------------------------------------
+
+using torch::Tensor;
+using OptTensor = c10::optional<Tensor>;
+
+// a named argument of an entry point; t == nullptr when it was not passed
+struct NormArg {
+  const char* name;
+  const Tensor* t;
+};
+inline NormArg arg(const char* name, const Tensor& t) { return {name, &t}; }
+inline NormArg arg(const char* name, const OptTensor& t) {
+  return {name, t.has_value() ? &*t : nullptr};
+}
+
+template <typename T>
+inline T* ptr(const Tensor& t) {
+  return t.defined() ? static_cast<T*>(t.data_ptr()) : nullptr;
+}
+template <typename T>
+inline T* ptr(const OptTensor& t) {
+  return t.has_value() ? static_cast<T*>(t->data_ptr()) : nullptr;
+}
+
+// Everything the kernels take for granted, checked once for both entry
+// points before anything is allocated or launched.  x fixes device, dtype
+// and [rows, D]; like_x are full activations (dy, resid, dresid), per_col
+// the [D] parameters (w, b), per_row the fp32 row statistics (mean, rstd).
+// Returns rows.
+int64_t check_norm_args(const char* fn, const Tensor& x,
+                        std::initializer_list<NormArg> like_x,
+                        std::initializer_list<NormArg> per_col,
+                        std::initializer_list<NormArg> per_row) {
+  TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 ||
+              x.scalar_type() == at::kFloat,
+              fn, ": x must be bf16 or fp32, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1, fn, ": x needs a last dim to normalize over");
+  const int64_t D = x.size(-1);
+  const int vec = x.scalar_type() == at::kBFloat16 ? VecIO<bf16>::VEC
+                                                   : VecIO<float>::VEC;
+  TORCH_CHECK(D > 0 && D <= INT_MAX, fn, ": last dim of x is ", D,
+              ", must be in [1, INT_MAX]");
+  TORCH_CHECK(D % vec == 0, fn, ": last dim of x is ", D,
+              ", must be a multiple of ", vec, " (16 B vector I/O)");
+  const int64_t rows = x.numel() / D;
+  // vec_io: read or written 16 B at a time from its base pointer
+  auto check = [&](const NormArg& a, at::ScalarType dtype, bool vec_io) {
+    TORCH_CHECK(a.t->is_cuda() && a.t->device() == x.device(), fn, ": ",
+                a.name, " is on ", a.t->device(), ", x on ", x.device());
+    TORCH_CHECK(a.t->is_contiguous(), fn, ": ", a.name,
+                " must be contiguous");
+    TORCH_CHECK(a.t->scalar_type() == dtype, fn, ": ", a.name, " must be ",
+                dtype, ", got ", a.t->scalar_type());
+    TORCH_CHECK(!vec_io ||
+                reinterpret_cast<uintptr_t>(a.t->data_ptr()) % 16 == 0,
+                fn, ": ", a.name, " must be 16-byte aligned");
+  };
+  check(arg("x", x), x.scalar_type(), true);
+  for (const NormArg& a : like_x) {
+    if (a.t == nullptr) continue;
+    check(a, x.scalar_type(), true);
+    TORCH_CHECK(a.t->sizes() == x.sizes(), fn, ": ", a.name, " has shape ",
+                a.t->sizes(), ", x has ", x.sizes());
+  }
+  for (const NormArg& a : per_col) {
+    if (a.t == nullptr) continue;
+    check(a, x.scalar_type(), true);
+    TORCH_CHECK(a.t->numel() == D, fn, ": ", a.name, " has ",
+                a.t->numel(), " elements, last dim of x is ", D);
+  }
+  for (const NormArg& a : per_row) {
+    if (a.t == nullptr) continue;
+    check(a, at::kFloat, false);
+    TORCH_CHECK(a.t->numel() == rows, fn, ": ", a.name, " has ",
+                a.t->numel(), " elements, x has ", rows, " rows");
+  }
+  return rows;
+}
+
 }  // namespace
 
-std::vector<torch::Tensor> layernorm_bwd2(torch::Tensor dy, torch::Tensor x,
-                                          torch::Tensor w,
-                                          torch::Tensor mean,
-                                          torch::Tensor rstd) {
-  const int D = x.size(-1);
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              dy.scalar_type() == x.scalar_type(),
-              "layernorm_bwd2: dy/w dtype must match x");
-  const int64_t rows = x.numel() / D;
-  TORCH_CHECK(D % 2 == 0);
-  auto dx = torch::empty_like(x);
-  auto dw32 = torch::zeros({D}, x.options().dtype(at::kFloat));
-  auto db32 = torch::zeros({D}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  DISPATCH_FLOAT(x, "layernorm_bwd2", [&] {
-    norm_bwd_v2_launch<scalar_t, true>(
-        (const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
-        (const scalar_t*)w.data_ptr(), mean.data_ptr<float>(),
-        rstd.data_ptr<float>(), (scalar_t*)dx.data_ptr(),
-        dw32.data_ptr<float>(), db32.data_ptr<float>(), rows, D, stream);
-  });
-  return {dx, dw32.to(w.scalar_type()), db32.to(w.scalar_type())};
+// y = norm(x [+ resid]) * w [+ b]; LayerNorm when b is given, else RMSNorm.
+// Returns {y, s = x + resid (if resid), mean (if b), rstd}; the statistics
+// are fp32 of x's shape without the last dim.
+std::vector<Tensor> norm_fwd(Tensor x, OptTensor resid, Tensor w,
+                             OptTensor b, double eps) {
+  const bool ln = b.has_value(), res = resid.has_value();
+  const int64_t rows = check_norm_args(
+      "norm_fwd", x, {arg("resid", resid)}, {arg("w", w), arg("b", b)}, {});
+  const int D = (int)x.size(-1);
+  const auto row_sizes = x.sizes().slice(0, x.dim() - 1);
+  const auto stat_opts = x.options().dtype(at::kFloat);
+  Tensor y = torch::empty_like(x), s, mean;
+  if (res) s = torch::empty_like(x);
+  if (ln) mean = torch::empty(row_sizes, stat_opts);
+  Tensor rstd = torch::empty(row_sizes, stat_opts);
+  if (rows > 0) {
+    auto stream = hetu_current_stream();
+    DISPATCH_FLOAT(x, "norm_fwd", [&] {
+      using T = scalar_t;
+      auto kernel =
+          ln ? (res ? norm_fwd_kernel<T, true, true>
+                    : norm_fwd_kernel<T, true, false>)
+             : (res ? norm_fwd_kernel<T, false, true>
+                    : norm_fwd_kernel<T, false, false>);
+      hipLaunchKernelGGL(kernel, dim3(row_grid(rows)), dim3(BLOCK), 0,
+                         stream, ptr<const T>(x), ptr<const T>(resid),
+                         ptr<const T>(w), ptr<const T>(b), ptr<T>(y),
+                         ptr<T>(s), ptr<float>(mean), ptr<float>(rstd),
+                         rows, D, (float)eps);
+    });
+  }
+  std::vector<Tensor> out{y};
+  if (res) out.push_back(s);
+  if (ln) out.push_back(mean);
+  out.push_back(rstd);
+  return out;
 }
 
-std::vector<torch::Tensor> rmsnorm_bwd2(torch::Tensor dy, torch::Tensor x,
-                                        torch::Tensor w,
-                                        torch::Tensor rstd) {
-  const int D = x.size(-1);
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              dy.scalar_type() == x.scalar_type(),
-              "rmsnorm_bwd2: dy/w dtype must match x");
-  const int64_t rows = x.numel() / D;
-  TORCH_CHECK(D % 2 == 0);
-  auto dx = torch::empty_like(x);
-  auto dw32 = torch::zeros({D}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  DISPATCH_FLOAT(x, "rmsnorm_bwd2", [&] {
-    norm_bwd_v2_launch<scalar_t, false>(
-        (const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
-        (const scalar_t*)w.data_ptr(), nullptr, rstd.data_ptr<float>(),
-        (scalar_t*)dx.data_ptr(), dw32.data_ptr<float>(), nullptr, rows,
-        D, stream);
-  });
-  return {dx, dw32.to(w.scalar_type())};
-}
-
-
-// ---- fused residual-add + LayerNorm (transformer pre-norm hot path) ----
-// fwd: s = x + resid; y = LN(s).  Returns {y, s, mean, rstd}.
-std::vector<torch::Tensor> layernorm_fwd_res(torch::Tensor x,
-                                             torch::Tensor resid,
-                                             torch::Tensor w,
-                                             torch::Tensor b, double eps) {
-  const int D = x.size(-1);
-  const int64_t rows = x.numel() / D;
-  TORCH_CHECK(D % 8 == 0, "layernorm: D must be a multiple of 8");
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              b.scalar_type() == x.scalar_type() &&
-              resid.scalar_type() == x.scalar_type(),
-              "layernorm_fwd_res: dtype mismatch");
-  TORCH_CHECK(resid.numel() == x.numel());
-  auto y = torch::empty_like(x);
-  auto s_out = torch::empty_like(x);
-  auto mean = torch::empty({rows}, x.options().dtype(at::kFloat));
-  auto rstd = torch::empty({rows}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  DISPATCH_FLOAT(x, "layernorm_fwd_res", [&] {
-    hipLaunchKernelGGL((layernorm_fwd_kernel<scalar_t, true>),
-                       dim3(row_grid(rows)), dim3(BLOCK), 0, stream,
-                       (const scalar_t*)x.data_ptr(),
-                       (const scalar_t*)resid.data_ptr(),
-                       (const scalar_t*)w.data_ptr(),
-                       (const scalar_t*)b.data_ptr(),
-                       (scalar_t*)y.data_ptr(),
-                       (scalar_t*)s_out.data_ptr(),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       rows, D, (float)eps);
-  });
-  auto row_sizes = at::IntArrayRef(x.sizes().begin(), x.sizes().end() - 1);
-  return {y, s_out, mean.view(row_sizes), rstd.view(row_sizes)};
-}
-
-// bwd: given dy (grad of y) and optional ds_ext (grad of s from its other
-// consumers), returns {dsum = dLN/ds + ds_ext, dw, db} — dsum is the grad
-// of BOTH x and resid.
-std::vector<torch::Tensor> layernorm_bwd2_res(torch::Tensor dy,
-                                              torch::Tensor s,
-                                              torch::Tensor w,
-                                              torch::Tensor mean,
-                                              torch::Tensor rstd,
-                                              torch::Tensor ds_ext) {
-  const int D = s.size(-1);
-  TORCH_CHECK(w.scalar_type() == s.scalar_type() &&
-              dy.scalar_type() == s.scalar_type(),
-              "layernorm_bwd2_res: dy/w dtype must match s");
-  const int64_t rows = s.numel() / D;
-  TORCH_CHECK(D % 2 == 0);
-  auto dx = torch::empty_like(s);
-  auto dw32 = torch::zeros({D}, s.options().dtype(at::kFloat));
-  auto db32 = torch::zeros({D}, s.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  const bool has_ext = ds_ext.defined() && ds_ext.numel() > 0;
-  DISPATCH_FLOAT(s, "layernorm_bwd2_res", [&] {
-    norm_bwd_v2_launch<scalar_t, true>(
-        (const scalar_t*)dy.data_ptr(), (const scalar_t*)s.data_ptr(),
-        (const scalar_t*)w.data_ptr(), mean.data_ptr<float>(),
-        rstd.data_ptr<float>(), (scalar_t*)dx.data_ptr(),
-        dw32.data_ptr<float>(), db32.data_ptr<float>(), rows, D, stream,
-        has_ext ? (const scalar_t*)ds_ext.data_ptr() : nullptr);
-  });
-  return {dx, dw32.to(w.scalar_type()), db32.to(w.scalar_type())};
-}
-
-
-// ---- fused residual-add + RMSNorm (Llama pre-norm hot path) ------------
-std::vector<torch::Tensor> rmsnorm_fwd_res(torch::Tensor x,
-                                           torch::Tensor resid,
-                                           torch::Tensor w, double eps) {
-  const int D = x.size(-1);
-  const int64_t rows = x.numel() / D;
-  TORCH_CHECK(D % 8 == 0, "rmsnorm: D must be a multiple of 8");
-  TORCH_CHECK(w.scalar_type() == x.scalar_type() &&
-              resid.scalar_type() == x.scalar_type(),
-              "rmsnorm_fwd_res: dtype mismatch");
-  auto y = torch::empty_like(x);
-  auto s_out = torch::empty_like(x);
-  auto rstd = torch::empty({rows}, x.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  DISPATCH_FLOAT(x, "rmsnorm_fwd_res", [&] {
-    hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, true>),
-                       dim3(row_grid(rows)), dim3(BLOCK), 0, stream,
-                       (const scalar_t*)x.data_ptr(),
-                       (const scalar_t*)resid.data_ptr(),
-                       (const scalar_t*)w.data_ptr(),
-                       (scalar_t*)y.data_ptr(),
-                       (scalar_t*)s_out.data_ptr(),
-                       rstd.data_ptr<float>(), rows, D, (float)eps);
-  });
-  auto row_sizes = at::IntArrayRef(x.sizes().begin(), x.sizes().end() - 1);
-  return {y, s_out, rstd.view(row_sizes)};
-}
-
-std::vector<torch::Tensor> rmsnorm_bwd2_res(torch::Tensor dy,
-                                            torch::Tensor s,
-                                            torch::Tensor w,
-                                            torch::Tensor rstd,
-                                            torch::Tensor ds_ext) {
-  const int D = s.size(-1);
-  TORCH_CHECK(w.scalar_type() == s.scalar_type() &&
-              dy.scalar_type() == s.scalar_type(),
-              "rmsnorm_bwd2_res: dy/w dtype must match s");
-  const int64_t rows = s.numel() / D;
-  TORCH_CHECK(D % 2 == 0);
-  auto dx = torch::empty_like(s);
-  auto dw32 = torch::zeros({D}, s.options().dtype(at::kFloat));
-  auto stream = hetu_current_stream();
-  const bool has_ext = ds_ext.defined() && ds_ext.numel() > 0;
-  DISPATCH_FLOAT(s, "rmsnorm_bwd2_res", [&] {
-    norm_bwd_v2_launch<scalar_t, false>(
-        (const scalar_t*)dy.data_ptr(), (const scalar_t*)s.data_ptr(),
-        (const scalar_t*)w.data_ptr(), nullptr, rstd.data_ptr<float>(),
-        (scalar_t*)dx.data_ptr(), dw32.data_ptr<float>(), nullptr, rows,
-        D, stream,
-        has_ext ? (const scalar_t*)ds_ext.data_ptr() : nullptr);
-  });
-  return {dx, dw32.to(w.scalar_type())};
+// Backward of norm_fwd over x (the sum s when a residual was fused);
+// LayerNorm when mean is given.  dresid, the grad of s from its other
+// consumers, is added into dx.  Returns {dx, dw, db (if mean)}: dx is the
+// grad of both x and resid, dw/db are summed in fp32 and cast to w's dtype.
+std::vector<Tensor> norm_bwd(Tensor dy, Tensor x, Tensor w, OptTensor mean,
+                             Tensor rstd, OptTensor dresid) {
+  const bool ln = mean.has_value();
+  const int64_t rows = check_norm_args(
+      "norm_bwd", x, {arg("dy", dy), arg("dresid", dresid)}, {arg("w", w)},
+      {arg("mean", mean), arg("rstd", rstd)});
+  const int D = (int)x.size(-1);
+  const auto acc_opts = x.options().dtype(at::kFloat);
+  Tensor dx = torch::empty_like(x), db32;
+  Tensor dw32 = torch::zeros({D}, acc_opts);
+  if (ln) db32 = torch::zeros({D}, acc_opts);
+  if (rows > 0) {
+    auto stream = hetu_current_stream();
+    DISPATCH_FLOAT(x, "norm_bwd", [&] {
+      using T = scalar_t;
+      auto launch = ln ? norm_bwd_launch<T, true> : norm_bwd_launch<T, false>;
+      launch(ptr<const T>(dy), ptr<const T>(x), ptr<const T>(w),
+             ptr<const float>(mean), ptr<const float>(rstd),
+             ptr<const T>(dresid), ptr<T>(dx), ptr<float>(dw32),
+             ptr<float>(db32), rows, D, stream);
+    });
+  }
+  std::vector<Tensor> out{dx, dw32.to(w.scalar_type())};
+  if (ln) out.push_back(db32.to(w.scalar_type()));
+  return out;
 }

@@ -61,10 +61,10 @@ def main():
     print("== memory-bound kernels (TB/s) ==")
     x = torch.randn(16384, 4096, dtype=torch.bfloat16, device=dev)
     w1 = torch.randn(4096, dtype=torch.bfloat16, device=dev)
-    t = bench(lambda: F.ext().rmsnorm_fwd(x, w1, 1e-6))
+    t = bench(lambda: F.rmsnorm_fwd(x, w1, 1e-6))
     print(f"  rmsnorm fwd 16k x 4k: {2*x.numel()*2/t/1e12:6.2f} TB/s")
-    y, rstd = F.ext().rmsnorm_fwd(x, w1, 1e-6)
-    t = bench(lambda: F.ext().rmsnorm_bwd(y, x, w1, rstd))
+    y, rstd = F.rmsnorm_fwd(x, w1, 1e-6)
+    t = bench(lambda: F.rmsnorm_bwd(y, x, w1, rstd))
     print(f"  rmsnorm bwd: {4*x.numel()*2/t/1e12:6.2f} TB/s")
     big = torch.randn(8192, 16384, dtype=torch.bfloat16, device=dev)
     t = bench(lambda: F.ext().swiglu_fwd(big))

@@ -65,6 +65,143 @@ class TestNorms:
         _close(dw, dwr, rtol=5e-2, atol=5e-2, what="ln dw")
         _close(db, dbr, rtol=5e-2, atol=5e-2, what="ln db")
 
+    def test_norm_bwd_matches_fp32_torch(self):
+        """Backward at a training-sized tile against the torch branch run
+        in fp32 on the same inputs and the same row statistics."""
+        torch.manual_seed(1)
+        R, D = 2048, 4096
+        x = torch.randn(R, D, dtype=torch.bfloat16, device=dev())
+        w = torch.randn(D, dtype=torch.bfloat16, device=dev())
+        b = torch.randn(D, dtype=torch.bfloat16, device=dev())
+        dy = torch.randn(R, D, dtype=torch.bfloat16, device=dev())
+        dyf, xf, wf = dy.cpu().float(), x.cpu().float(), w.cpu().float()
+        y, mean, rstd = F.layernorm_fwd(x, w, b, 1e-5)
+        got = F.layernorm_bwd(dy, x, w, mean, rstd)
+        ref = F.layernorm_bwd(dyf, xf, wf, mean.cpu(), rstd.cpu())
+        for n, t, tr in zip(("dx", "dw", "db"), got, ref):
+            _close(t, tr, rtol=2e-2, atol=2e-2, what=f"ln bwd {n}")
+        yr, rs = F.rmsnorm_fwd(x, w, 1e-6)
+        got = F.rmsnorm_bwd(dy, x, w, rs)
+        ref = F.rmsnorm_bwd(dyf, xf, wf, rs.cpu())
+        for n, t, tr in zip(("dx", "dw"), got, ref):
+            _close(t, tr, rtol=2e-2, atol=2e-2, what=f"rms bwd {n}")
+
+    # Shapes at the kernels' edges.  D = 0 stands for one 16 B vector (8
+    # bf16 / 4 fp32): one row, one active lane.  (5, 520): rows not a
+    # multiple of the 4 waves per block, and a second, mostly empty
+    # 512-column dw/db block.  (65, 1032): rows_chunk is 64, so a second
+    # row block of one row; D no multiple of a wave's 512-element stride.
+    @pytest.mark.parametrize("shape", [(1, 0), (5, 520), (65, 1032)])
+    @pytest.mark.parametrize("ln", [True, False], ids=["ln", "rms"])
+    @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+    def test_norm_edge_shapes(self, dtype, ln, shape):
+        torch.manual_seed(2)
+        R = shape[0]
+        D = shape[1] or (8 if dtype == torch.bfloat16 else 4)
+        x, r, dy, ds = (torch.randn(R, D, dtype=dtype, device=dev())
+                        for _ in range(4))
+        w = torch.randn(D, dtype=dtype, device=dev())
+        b = torch.randn(D, dtype=dtype, device=dev())
+
+        def f32(*ts):
+            return [t.cpu().float() for t in ts]
+
+        def fwd(x, r, w, b):
+            if ln:
+                return (F.layernorm_fwd(x, w, b, 1e-5) if r is None else
+                        F.layernorm_fwd_res(x, r, w, b, 1e-5))
+            return (F.rmsnorm_fwd(x, w, 1e-6) if r is None else
+                    F.rmsnorm_fwd_res(x, r, w, 1e-6))
+
+        def bwd(dy, s, w, stats, ds):
+            if ln:
+                return F.layernorm_bwd_res(dy, s, w, *stats, ds)
+            return F.rmsnorm_bwd_res(dy, s, w, *stats, ds)
+
+        for res in (False, True):
+            out = fwd(x, r if res else None, w, b)
+            ref = fwd(*f32(x), f32(r)[0] if res else None, *f32(w, b))
+            assert len(out) == len(ref) == 1 + res + ln + 1
+            for i, (t, tr) in enumerate(zip(out, ref)):
+                assert t.shape == tr.shape
+                _close(t, tr, what=f"fwd res={res} out {i}")
+            # backward over what the forward normalized, with its statistics
+            s, stats = (out[1] if res else x), out[1 + res:]
+            got = bwd(dy, s, w, stats, ds if res else None)
+            ref = bwd(*f32(dy, s, w), f32(*stats),
+                      f32(ds)[0] if res else None)
+            assert len(got) == len(ref) == 2 + ln
+            _close(got[0], ref[0], what=f"dx res={res}")
+            for t, tr in zip(got[1:], ref[1:]):
+                assert t.dtype == dtype and t.shape == (D,)
+                _close(t, tr, rtol=5e-2, atol=5e-2, what=f"dw/db res={res}")
+            if not res:
+                # the plain entry points are the same call without dresid
+                plain = (F.layernorm_bwd if ln else F.rmsnorm_bwd)(
+                    dy, x, w, *stats)
+                assert torch.equal(plain[0], got[0])
+
+    @pytest.mark.parametrize("ln", [True, False], ids=["ln", "rms"])
+    @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+    def test_norm_no_rows(self, dtype, ln):
+        """rows == 0: empty outputs, zero dw/db, nothing launched and no
+        error left pending for the next kernel."""
+        x, r, dy, ds = (torch.empty(0, 64, dtype=dtype, device=dev())
+                        for _ in range(4))
+        w = torch.randn(64, dtype=dtype, device=dev())
+        b = torch.randn(64, dtype=dtype, device=dev())
+        for res in (False, True):
+            out = F.ext().norm_fwd(x, r if res else None, w,
+                                   b if ln else None, 1e-5)
+            assert len(out) == 1 + res + ln + 1
+            for t in out[:1 + res]:
+                assert t.shape == (0, 64) and t.dtype == dtype
+            for t in out[1 + res:]:
+                assert t.shape == (0,) and t.dtype == torch.float32
+            got = F.ext().norm_bwd(dy, x, w, out[-2] if ln else None,
+                                   out[-1], ds if res else None)
+            assert len(got) == 2 + ln
+            assert got[0].shape == (0, 64) and got[0].dtype == dtype
+            for t in got[1:]:
+                assert t.shape == (64,) and t.dtype == dtype
+                assert not t.any()
+        ones = torch.ones(4, 64, dtype=dtype, device=dev())
+        y, _ = F.rmsnorm_fwd(ones, ones[0], 0.0)
+        torch.cuda.synchronize()
+        _close(y, ones, what="kernel after the empty calls")
+
+    def test_norm_rejects_bad_arguments(self):
+        """Each bad argument is refused by name before anything is
+        launched; the entry points are called directly, as scripts do."""
+        E = F.ext()
+        bf, d = torch.bfloat16, dev()
+        x = torch.randn(4, 16, dtype=bf, device=d)
+        w = torch.ones(16, dtype=bf, device=d)
+        rstd = torch.ones(4, device=d)
+        # passes the old `D % 2` check, fails the 8-element vector width
+        x1028 = torch.randn(2, 1028, dtype=bf, device=d)
+        with pytest.raises(RuntimeError, match="1028.*multiple of 8"):
+            E.norm_bwd(x1028, x1028, torch.ones(1028, dtype=bf, device=d),
+                       None, torch.ones(2, device=d), None)
+        xt = torch.randn(16, 4, dtype=bf, device=d).t()
+        assert xt.shape == x.shape and not xt.is_contiguous()
+        with pytest.raises(RuntimeError, match="x must be contiguous"):
+            E.norm_fwd(xt, None, w, None, 1e-6)
+        with pytest.raises(RuntimeError, match="w has 8 elements"):
+            E.norm_fwd(x, None, w[:8], None, 1e-6)
+        with pytest.raises(RuntimeError, match="rstd must be Float"):
+            E.norm_bwd(x, x, w, None, rstd.double(), None)
+        with pytest.raises(RuntimeError, match="dresid has shape"):
+            E.norm_bwd(x, x, w, None, rstd, x[:2])
+        with pytest.raises(RuntimeError, match="w is on cpu"):
+            E.norm_fwd(x, None, w.cpu(), None, 1e-6)
+        torch.cuda.synchronize()
+        # the same calls with the argument put right go through
+        y, r2 = E.norm_fwd(x, None, w, None, 1e-6)
+        dx, dw = E.norm_bwd(x, x, w, None, r2, x)
+        torch.cuda.synchronize()
+        assert y.shape == dx.shape == x.shape and dw.shape == w.shape
+
 
 class TestElementwise:
     def test_swiglu(self):
@@ -381,26 +518,6 @@ class TestVocabParallelCEKernels:
         refd = (sm - onehot) * scale[:, None]
         _close(dl, refd, rtol=3e-2, atol=3e-3, what="vp_ce_bwd")
 
-    def test_norm_bwd_v2_matches_v1(self):
-        torch.manual_seed(1)
-        R, D = 2048, 4096
-        x = torch.randn(R, D, dtype=torch.bfloat16, device=dev())
-        w = torch.randn(D, dtype=torch.bfloat16, device=dev())
-        b = torch.randn(D, dtype=torch.bfloat16, device=dev())
-        dy = torch.randn(R, D, dtype=torch.bfloat16, device=dev())
-        y, mean, rstd = F.layernorm_fwd(x, w, b, 1e-5)
-        a = F.ext().layernorm_bwd(dy, x, w, mean, rstd)
-        v2 = F.ext().layernorm_bwd2(dy, x, w, mean, rstd)
-        for n, (t1, t2) in zip(("dx", "dw", "db"), zip(a, v2)):
-            _close(t2, t1.float(), rtol=2e-2, atol=2e-2,
-                   what=f"ln bwd2 {n}")
-        yr, rs = F.rmsnorm_fwd(x, w, 1e-6)
-        a = F.ext().rmsnorm_bwd(dy, x, w, rs)
-        v2 = F.ext().rmsnorm_bwd2(dy, x, w, rs)
-        for n, (t1, t2) in zip(("dx", "dw"), zip(a, v2)):
-            _close(t2, t1.float(), rtol=2e-2, atol=2e-2,
-                   what=f"rms bwd2 {n}")
-
 
 class TestGenerator:
     def test_fa_prefill_matches_fp32_path(self):
@@ -541,7 +658,7 @@ def test_varlen_single_kernel():
 
 @pytest.mark.gpu
 def test_fused_add_ln_kernels():
-    """layernorm_fwd_res / layernorm_bwd2_res numerics vs composed."""
+    """layernorm_fwd_res / layernorm_bwd_res numerics vs composed."""
     import hetu_amd.ops.functional as F
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
