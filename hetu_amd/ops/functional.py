@@ -545,7 +545,10 @@ def _attn_ref_bwd(dout, q, k, v, out, lse, causal, scale):
 # place (ops/hip/attention_decode.hip; docs/KERNELS.md "Decode attention")
 # ---------------------------------------------------------------------------
 
-_DECODE_IMPLS = (None, "torch", "hip")
+_DECODE_IMPLS = (None, "torch", "hip", "mfma")
+# what impl=None means: auto | hip | mfma (HETU_AMD_WGRAD's style)
+_HETU_DECODE = os.environ.get("HETU_AMD_DECODE", "auto")
+_DECODE_ENV = ("auto", "hip", "mfma")
 
 
 def _decode_hip_ineligible(q, k_cache, v_cache, kv_len) -> Optional[str]:
@@ -588,6 +591,36 @@ def _decode_auto_hip(B: int, Hkv: int, L: int) -> bool:
     2.1-52x.  Shapes between and beyond the measured ones pass without
     having been timed: that part is extrapolated."""
     return True
+
+
+def _decode_auto_mfma(G: int, D: int, B: int, Hkv: int, L: int) -> bool:
+    """Where the MFMA kernel (ops/hip/attention_decode_mfma.hip) was ahead of
+    the VALU kernel with disjoint min-max ranges in
+    scripts/bench_decode_attn.py (profiles/r09_decode_mfma.md).
+    Measured, bf16, B in {1, 16, 64} x kv_len in {2048, 8192}, 7 rounds x 20
+    calls: H/Hkv 32/4 and 64/8 (G = 8, D = 128) ahead on all 12 rows by
+    1.15-1.47x; 32/1 (MQA, G = 32, D = 128) on all 6 by 1.75-4.30x; 24/4
+    (G = 6, D = 64) on all 6 by 1.20-1.68x.  The control 32/8 (G = 4) is
+    within 1-7 %: ahead with disjoint ranges on 4 of 6 rows in the recorded
+    run and on 2 of 6 in an earlier run of the same build, only B = 1 / 8192
+    in both, the ranges 0.001-0.01 ms apart.  That is run-to-run movement,
+    not a measured win, so G <= 4 stays on the VALU kernel as a whole.
+    Extrapolated, not timed: G = 5 and 7 (the VALU kernel runs them as 8
+    heads, as it does G = 6 and 8), every G from 9 up other than 32, D = 64
+    at G other than 6, other B and Hkv, and kv_len between and beyond 2048
+    and 8192.  Caches shorter than 2048 rows were not timed and stay on the
+    VALU kernel."""
+    return G >= 5 and L >= 2048
+
+
+def _decode_env(switch=None) -> str:
+    """HETU_AMD_DECODE: which kernel impl=None takes where a HIP kernel is
+    eligible; "auto" asks _decode_auto_mfma."""
+    switch = _HETU_DECODE if switch is None else switch
+    if switch not in _DECODE_ENV:
+        raise ValueError(f"HETU_AMD_DECODE must be one of {_DECODE_ENV}, "
+                         f"got {switch!r}")
+    return switch
 
 
 def _decode_check_shapes(q, k_cache, v_cache):
@@ -645,7 +678,7 @@ def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None) -> bool:
     the Python int, which keeps the torch branch on its slicing form."""
     if impl == "torch":
         return False
-    if impl == "hip":
+    if impl in ("hip", "mfma"):
         return True
     return (_decode_hip_ineligible(q, k_cache, v_cache, kv_len) is None
             and "fa" not in _TORCH_FB
@@ -666,15 +699,18 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
     exp(scale * q.k_j), the definition flash_attn_fwd uses); kv_len == 0
     gives out = 0, lse = -inf.
 
-    impl: "hip" = the split-KV kernel (bf16, D 64 or 128, GPU; an error on
-    anything else, never a fallback); "torch" = fp32 torch math; None = the
-    kernel where it is eligible and measured ahead, else torch.  num_splits
+    impl: "hip" = the split-KV VALU kernel (bf16, D 64 or 128, GPU; an error
+    on anything else, never a fallback); "mfma" = the MFMA kernel for wide
+    GQA groups and MQA, same contract and eligibility, any H / Hkv; "torch" =
+    fp32 torch math; None = a kernel where one is eligible and measured
+    ahead (the MFMA one where _decode_auto_mfma says so, HETU_AMD_DECODE=
+    hip|mfma|auto overrides that choice), else torch.  num_splits
     (HIP only): 0 lets the launcher choose from B, Hkv, L and the CU count
     (never from the values of kv_len, so a captured graph stays valid);
     >= 1 forces it."""
     if impl not in _DECODE_IMPLS:
-        raise ValueError("flash_attn_decode: impl must be None, 'torch' or "
-                         f"'hip', got {impl!r}")
+        raise ValueError("flash_attn_decode: impl must be None, 'torch', "
+                         f"'hip' or 'mfma', got {impl!r}")
     _decode_check_shapes(q, k_cache, v_cache)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
@@ -682,14 +718,22 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
         return _decode_torch(q, k_cache, v_cache, kv_len, scale)
     why = _decode_hip_ineligible(q, k_cache, v_cache, kv_len)
     if why is not None:
-        raise RuntimeError(f"flash_attn_decode(impl='hip'): {why}")
+        raise RuntimeError(f"flash_attn_decode(impl={impl!r}): {why}")
+    if impl is None:
+        impl = _decode_env()
+        if impl == "auto":
+            impl = "mfma" if _decode_auto_mfma(
+                q.shape[1] // k_cache.shape[1], q.shape[2], q.shape[0],
+                k_cache.shape[1], k_cache.shape[2]) else "hip"
     if not isinstance(kv_len, torch.Tensor):
         # a fill kernel, not a host-to-device copy
         n = min(max(int(kv_len), 0), k_cache.shape[2])
         kv_len = torch.full((q.shape[0],), n, dtype=torch.int32,
                             device=q.device)
-    out, lse = ext().flash_attn_decode(q, k_cache, v_cache, kv_len,
-                                       float(scale), int(num_splits))
+    kernel = ext().flash_attn_decode_mfma if impl == "mfma" \
+        else ext().flash_attn_decode
+    out, lse = kernel(q, k_cache, v_cache, kv_len, float(scale),
+                      int(num_splits))
     return out, lse
 
 

@@ -30,15 +30,15 @@
 #include <ATen/hip/HIPContext.h>
 #include "ext_stream.h"
 #include "attention_common.h"
+#include "attention_decode.h"
 
 namespace {
 
-constexpr int DEC_BN = 64;             // keys per block tile
+// DEC_BN (attention_decode.h) is the block's key tile here
 constexpr int DEC_WAVES = 4;           // 16 keys of the tile each
 constexpr int DEC_THREADS = DEC_WAVES * WAVE;
 constexpr int DEC_WKEYS = DEC_BN / DEC_WAVES;
 constexpr int DEC_MAX_GC = 8;          // query heads per pass
-constexpr int DEC_MAX_SPLITS = 64;
 
 template <int CTRL>
 DEV float dec_dpp_add(float x) {
@@ -65,22 +65,6 @@ DEV float dec_dot2(u32 a, u32 b, float acc) {
                                          __builtin_bit_cast(v2bf, b), acc,
                                          false);
 }
-
-struct DecArgs {
-  const bf16* q;
-  const bf16* k;
-  const bf16* v;
-  const int* kv_len;
-  bf16* out;          // [B, H, D]
-  float* lse;         // [B, H]
-  float* ws_o;        // [B, H, ns, D], normalised partial outputs
-  float* ws_lse;      // [B, H, ns]
-  long long q_bs, q_hs;
-  long long k_bs, k_hs, k_rs;
-  long long v_bs, v_hs, v_rs;
-  int H, Hkv, L, ns;
-  float scale;
-};
 
 template <int D, int GC>
 __global__ __launch_bounds__(DEC_THREADS)
@@ -272,6 +256,8 @@ void fa_decode_kernel(DecArgs a) {
   }
 }
 
+}  // namespace
+
 // out[row] = sum_s exp(lse_s - lse) * o_s over the non-empty splits, in
 // split order; one block per (b, h), one thread per dim
 __global__ void fa_decode_merge_kernel(const float* __restrict__ ws_o,
@@ -299,7 +285,7 @@ __global__ void fa_decode_merge_kernel(const float* __restrict__ ws_o,
   if (d == 0) lse[row] = mx == -INFINITY ? -INFINITY : mx + logf(sum);
 }
 
-bool dec_aligned16(const void* p) {
+static bool dec_aligned16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
 
@@ -315,8 +301,6 @@ void dec_check_strides(const torch::Tensor& t, const char* what) {
               " is not 16-byte aligned");
 }
 
-}  // namespace
-
 int64_t decode_attn_tile() { return DEC_BN; }
 
 // the launcher's split count: B, Hkv, L and the CU count only (never the
@@ -330,12 +314,9 @@ int64_t decode_attn_num_splits(int64_t B, int64_t Hkv, int64_t L,
       1, std::min<int64_t>({want, tiles, (int64_t)DEC_MAX_SPLITS}));
 }
 
-std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
-                                             torch::Tensor k_cache,
-                                             torch::Tensor v_cache,
-                                             torch::Tensor kv_len,
-                                             double scale,
-                                             int64_t num_splits) {
+DecCall dec_prepare(const torch::Tensor& q, const torch::Tensor& k_cache,
+                    const torch::Tensor& v_cache, const torch::Tensor& kv_len,
+                    double scale, int64_t num_splits, int key_tile) {
   TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda() &&
               kv_len.is_cuda(),
               "flash_attn_decode: q, k_cache, v_cache and kv_len must be on "
@@ -362,12 +343,16 @@ std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
   TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 &&
               kv_len.size(0) == B && kv_len.is_contiguous(),
               "flash_attn_decode: kv_len must be a contiguous int32 [B]");
-  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && L < ((int64_t)1 << 31) - DEC_BN,
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535 &&
+              L < ((int64_t)1 << 31) - key_tile,
               "flash_attn_decode: B, Hkv or L too large");
   TORCH_CHECK(num_splits >= 0, "flash_attn_decode: num_splits must be >= 0");
-  auto out = torch::empty({B, H, D}, q.options());
-  auto lse = torch::empty({B, H}, q.options().dtype(at::kFloat));
-  if (B == 0 || H == 0) return {out, lse};
+  DecCall c;
+  c.B = B; c.H = H; c.Hkv = Hkv; c.D = D;
+  c.out = torch::empty({B, H, D}, q.options());
+  c.lse = torch::empty({B, H}, q.options().dtype(at::kFloat));
+  c.empty = B == 0 || H == 0;
+  if (c.empty) return c;
   dec_check_strides(q, "q");
   dec_check_strides(k_cache, "k_cache");
   dec_check_strides(v_cache, "v_cache");
@@ -376,19 +361,18 @@ std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
   const int ns = (int)(num_splits > 0
                            ? std::min<int64_t>(num_splits, 1 << 16)
                            : decode_attn_num_splits(B, Hkv, L, cus));
-  torch::Tensor ws;
-  DecArgs a;
+  DecArgs& a = c.a;
   a.q = (const bf16*)q.data_ptr();
   a.k = (const bf16*)k_cache.data_ptr();
   a.v = (const bf16*)v_cache.data_ptr();
   a.kv_len = kv_len.data_ptr<int>();
-  a.out = (bf16*)out.data_ptr();
-  a.lse = lse.data_ptr<float>();
+  a.out = (bf16*)c.out.data_ptr();
+  a.lse = c.lse.data_ptr<float>();
   a.ws_o = nullptr;
   a.ws_lse = nullptr;
   if (ns > 1) {                        // caching allocator, stream-ordered
-    ws = torch::empty({B * H * ns * (D + 1)}, lse.options());
-    a.ws_o = ws.data_ptr<float>();
+    c.ws = torch::empty({B * H * ns * (D + 1)}, c.lse.options());
+    a.ws_o = c.ws.data_ptr<float>();
     a.ws_lse = a.ws_o + B * H * ns * D;
   }
   a.q_bs = q.stride(0); a.q_hs = q.stride(1);
@@ -398,11 +382,30 @@ std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
   a.v_rs = v_cache.stride(2);
   a.H = (int)H; a.Hkv = (int)Hkv; a.L = (int)L; a.ns = ns;
   a.scale = (float)scale;
+  return c;
+}
 
-  const int64_t G = H / Hkv;
+void dec_merge_launch(const DecCall& c, hipStream_t stream) {
+  hipLaunchKernelGGL(fa_decode_merge_kernel, dim3((unsigned)(c.B * c.H)),
+                     dim3((unsigned)c.D), 0, stream, c.a.ws_o, c.a.ws_lse,
+                     c.a.out, c.a.lse, c.a.ns, (int)c.D);
+  HIP_CHECK(hipGetLastError());
+}
+
+std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
+                                             torch::Tensor k_cache,
+                                             torch::Tensor v_cache,
+                                             torch::Tensor kv_len,
+                                             double scale,
+                                             int64_t num_splits) {
+  DecCall c = dec_prepare(q, k_cache, v_cache, kv_len, scale, num_splits,
+                          DEC_BN);
+  if (c.empty) return {c.out, c.lse};
+  const DecArgs& a = c.a;
+  const int64_t D = c.D, G = c.H / c.Hkv;
   const int gc = G >= 5 ? 8 : G >= 3 ? 4 : (int)G;
   auto stream = hetu_current_stream();
-  const dim3 grid(ns, (unsigned)Hkv, (unsigned)B);
+  const dim3 grid(a.ns, (unsigned)c.Hkv, (unsigned)c.B);
 #define DEC_LAUNCH(DD, GG)                                                 \
   hipLaunchKernelGGL((fa_decode_kernel<DD, GG>), grid, dim3(DEC_THREADS),  \
                      0, stream, a)
@@ -418,11 +421,6 @@ std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
 #undef DEC_LAUNCH_D
 #undef DEC_LAUNCH
   HIP_CHECK(hipGetLastError());
-  if (ns > 1) {
-    hipLaunchKernelGGL(fa_decode_merge_kernel, dim3((unsigned)(B * H)),
-                       dim3((unsigned)D), 0, stream, a.ws_o, a.ws_lse, a.out,
-                       a.lse, ns, (int)D);
-    HIP_CHECK(hipGetLastError());
-  }
-  return {out, lse};
+  if (a.ns > 1) dec_merge_launch(c, stream);
+  return {c.out, c.lse};
 }

@@ -151,6 +151,14 @@ std::vector<torch::Tensor> flash_attn_decode(torch::Tensor q,
                                              torch::Tensor kv_len,
                                              double scale,
                                              int64_t num_splits);
+// attention_decode_mfma.hip
+int64_t decode_attn_mfma_tile();
+std::vector<torch::Tensor> flash_attn_decode_mfma(torch::Tensor q,
+                                                  torch::Tensor k_cache,
+                                                  torch::Tensor v_cache,
+                                                  torch::Tensor kv_len,
+                                                  double scale,
+                                                  int64_t num_splits);
 
 // embed_cache.cpp
 void register_embed_cache(pybind11::module& m);
@@ -221,6 +229,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_tile", &decode_attn_tile);
   m.def("decode_attn_num_splits", &decode_attn_num_splits);
   m.def("flash_attn_decode", &flash_attn_decode, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
+        py::arg("scale"), py::arg("num_splits") = 0);
+  m.def("decode_attn_mfma_tile", &decode_attn_mfma_tile);
+  m.def("flash_attn_decode_mfma", &flash_attn_decode_mfma, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
         py::arg("scale"), py::arg("num_splits") = 0);
 }

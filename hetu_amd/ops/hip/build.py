@@ -33,6 +33,7 @@ SOURCES = [
     "attention_bwd_v3.hip",
     "attention_bwd_v2.hip",
     "attention_decode.hip",
+    "attention_decode_mfma.hip",
     "quant.hip",
     "moe.hip",
     "ltgemm.cpp",
@@ -41,6 +42,14 @@ SOURCES = [
     "dataloader.cpp",
     "bindings.cpp",
 ]
+
+# per-source extra flags.  New kernels are compiled without the packed fp32
+# VALU ops (v_pk_{add,mul,fma}_f32); the older sources keep the code
+# generation they were measured with.
+EXTRA_FLAGS = {
+    "attention_decode_mfma.hip": ["-Xclang", "-target-feature", "-Xclang",
+                                  "-packed-fp32-ops"],
+}
 
 
 def _torch_paths():
@@ -105,7 +114,8 @@ def build(verbose: bool = True) -> str:
         src, obj = job
         if verbose:
             print("[hetu_amd build]", os.path.basename(src), flush=True)
-        subprocess.run(["hipcc", "-c", src, "-o", obj] + common_flags,
+        subprocess.run(["hipcc", "-c", src, "-o", obj] + common_flags
+                       + EXTRA_FLAGS.get(os.path.basename(src), []),
                        check=True)
 
     # the translation units are independent; one hipcc per core (MAX_JOBS

@@ -14,6 +14,11 @@ only reads) is timed in the same rounds.  Bytes that must move:
 2 * B * Hkv * kv_len * D * 2 (each cached K and V row once as bf16).
 The kernel belongs on the auto route for a shape only if its [min-max] range
 lies entirely below the composition's ("hip_wins").
+--mfma adds the MFMA kernel (impl="mfma", ops/hip/attention_decode_mfma.hip)
+as a further side of the same rounds; its baseline is the VALU kernel of the
+same run ("mfma_wins": its range lies entirely below the VALU kernel's), and
+--no-composition leaves the composition out (at G = 32 or 64 its
+repeat_interleave copies dominate the run).
 Needs a GPU; prints one JSON line per row and exits non-zero if a row that
 F.flash_attn_decode's auto rule sends to the kernel does not win, or if the
 two sides' outputs differ by more than two bf16 roundings of max|v|.
@@ -22,6 +27,7 @@ two sides' outputs differ by more than two bf16 roundings of max|v|.
                                         [--batches 1,16,64]
                                         [--lens 512,2048,8192] [--md FILE]
                                         [--shapes 32/32/128,32/8/128,16/16/64]
+                                        [--mfma] [--no-composition]
 """
 import argparse
 import json
@@ -71,7 +77,8 @@ def stats(ts):
             "min": round(min(ts), 4), "max": round(max(ts), 4)}
 
 
-def run_row(B, H, Hkv, D, n, seed, iters, rounds, dev):
+def run_row(B, H, Hkv, D, n, seed, iters, rounds, dev, mfma=False,
+            with_composition=True):
     g = torch.Generator(device=dev).manual_seed(seed)
     q = torch.randn(B, H, D, generator=g, device=dev).to(torch.bfloat16)
     k = torch.randn(B, Hkv, n, D, generator=g, device=dev).to(torch.bfloat16)
@@ -87,12 +94,26 @@ def run_row(B, H, Hkv, D, n, seed, iters, rounds, dev):
                                            torch.bfloat16),
         "copy": lambda: (k2.copy_(k), v2.copy_(v)),
     }
+    vmax = v.float().abs().max().item()
     oh = sides["hip"]()[0].float()
-    oc = sides["composition"]().squeeze(2).float()
-    max_diff = (oh - oc).abs().max().item()
-    # each side rounds its output to bf16 once: two roundings of max|v|
-    numerics_ok = max_diff <= 2 * 2.0 ** -9 * v.float().abs().max().item()
-    del oh, oc
+    max_diff, numerics_ok = 0.0, True
+    if with_composition:
+        oc = sides["composition"]().squeeze(2).float()
+        max_diff = (oh - oc).abs().max().item()
+        # each side rounds its output to bf16 once: two roundings of max|v|
+        numerics_ok = max_diff <= 2 * 2.0 ** -9 * vmax
+        del oc
+    else:
+        del sides["composition"]
+    mfma_diff = 0.0
+    if mfma:
+        sides["mfma"] = lambda: F.flash_attn_decode(q, k, v, kv_len, scale,
+                                                    impl="mfma")
+        # each kernel is within 3 * 2^-9 max|v| of the exact result
+        # (tests/decode_attn_oracle.py)
+        mfma_diff = (sides["mfma"]()[0].float() - oh).abs().max().item()
+        numerics_ok = numerics_ok and mfma_diff <= 6 * 2.0 ** -9 * vmax
+    del oh
     for fn in sides.values():
         window_ms(fn, 3)
     times = {s: [] for s in sides}
@@ -111,6 +132,15 @@ def run_row(B, H, Hkv, D, n, seed, iters, rounds, dev):
     for s, ts in times.items():
         res[s + "_ms"] = stats(ts)
     res["hip_tbps"] = round(nbytes / (med["hip"] * 1e-3) / 1e12, 3)
+    if mfma:
+        res["max_diff_mfma_vs_hip"] = mfma_diff
+        res["mfma_tbps"] = round(nbytes / (med["mfma"] * 1e-3) / 1e12, 3)
+        res["hip_over_mfma"] = round(med["hip"] / med["mfma"], 3)
+        res["mfma_wins"] = numerics_ok and max(times["mfma"]) < min(times["hip"])
+        res["auto_routes_mfma"] = F._decode_auto_mfma(H // Hkv, D, B, Hkv, n)
+    if not with_composition:
+        print(json.dumps(res), flush=True)
+        return res
     res["composition_tbps"] = round(
         nbytes / (med["composition"] * 1e-3) / 1e12, 3)
     # the copy moves the same bytes (and writes them as well)
@@ -142,6 +172,23 @@ def md_table(rows):
     return "\n".join(out) + "\n"
 
 
+def md_table_mfma(rows):
+    def rng(d):
+        return f"{d['median']:.4f} [{d['min']:.4f}-{d['max']:.4f}]"
+    out = ["| H/Hkv | D | B | kv_len | splits | VALU ms | MFMA ms | copy_ ms | "
+           "VALU TB/s | MFMA TB/s | VALU / MFMA | MFMA wins | auto |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        out.append(
+            f"| {r['H']}/{r['Hkv']} | {r['D']} | {r['B']} | {r['kv_len']} | "
+            f"{r['splits']} | {rng(r['hip_ms'])} | {rng(r['mfma_ms'])} | "
+            f"{rng(r['copy_ms'])} | {r['hip_tbps']:.3f} | "
+            f"{r['mfma_tbps']:.3f} | {r['hip_over_mfma']:.2f}x | "
+            f"{'yes' if r['mfma_wins'] else 'no'} | "
+            f"{'mfma' if r['auto_routes_mfma'] else 'valu'} |")
+    return "\n".join(out) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -152,6 +199,9 @@ def main():
         "/".join(str(x) for x in s) for s in HEAD_SHAPES),
         help="H/Hkv/D triples")
     ap.add_argument("--md", default="", help="also write a markdown table")
+    ap.add_argument("--mfma", action="store_true",
+                    help="add the MFMA kernel beside the VALU kernel")
+    ap.add_argument("--no-composition", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_decode_attn: needs a GPU")
@@ -163,20 +213,26 @@ def main():
         for B in (int(x) for x in args.batches.split(",")):
             for n in (int(x) for x in args.lens.split(",")):
                 res = run_row(B, H, Hkv, D, n, i, args.iters, args.rounds,
-                              dev)
+                              dev, args.mfma, not args.no_composition)
                 i += 1
                 rows.append(res)
                 tag = f"H={H}/{Hkv} D={D} B={B} kv_len={n}"
                 if not res["numerics_ok"]:
                     bad.append(f"{tag}: outputs differ by "
-                               f"{res['max_diff_hip_vs_composition']}")
-                if res["auto_routes_hip"] and not res["hip_wins"]:
+                               f"{res['max_diff_hip_vs_composition']} / "
+                               f"{res.get('max_diff_mfma_vs_hip', 0.0)}")
+                if args.mfma and res["auto_routes_mfma"] \
+                        and not res["mfma_wins"]:
+                    bad.append(f"{tag}: auto routes it to the MFMA kernel, "
+                               "whose range is not below the VALU kernel's")
+                if "hip_wins" in res and res["auto_routes_hip"] \
+                        and not res["hip_wins"]:
                     bad.append(f"{tag}: auto routes it to the kernel, whose "
                                "range is not below the composition's")
                 torch.cuda.empty_cache()
     if args.md:
         with open(args.md, "w") as fh:
-            fh.write(md_table(rows))
+            fh.write(md_table_mfma(rows) if args.mfma else md_table(rows))
     if bad:
         sys.exit("bench_decode_attn: " + "; ".join(bad))
 

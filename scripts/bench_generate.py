@@ -9,8 +9,12 @@ synchronises, so prefill and the first sample drop out; the first of
 `--rounds` rounds is warm-up and not reported.  Prints one JSON line per
 (batch, prompt) row: min / median / max over the rounds.  Needs a GPU.
 
+--mfma adds decode_impl="mfma" (ops/hip/attention_decode_mfma.hip) as a
+third generator; --kv-heads 4 makes the group G = 8, where it is meant to run.
+
     python scripts/bench_generate.py [--layers 4] [--new 64] [--rounds 4]
                                      [--rows 1x2048,16x2048,16x3900]
+                                     [--kv-heads 8] [--mfma]
 """
 import argparse
 import json
@@ -61,18 +65,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--rows", default="1x2048,16x2048,16x3900",
                     help="batch x prompt length")
+    ap.add_argument("--kv-heads", type=int, default=8)
+    ap.add_argument("--mfma", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_generate: needs a GPU")
     dev = torch.device("cuda", 0)
-    # Llama-7B width with 8 KV heads
-    cfg = LlamaConfig(n_layer=args.layers, n_head=32, n_kv_head=8,
+    # Llama-7B width with 8 KV heads (or --kv-heads)
+    cfg = LlamaConfig(n_layer=args.layers, n_head=32, n_kv_head=args.kv_heads,
                       hidden=4096, ffn_hidden=11008, vocab=32000,
                       max_seq=4096)
     state = llama_state(cfg, 11008)
     gens = {impl: LlamaGenerator(cfg, state, device=dev,
                                  dtype=torch.bfloat16, decode_impl=impl)
-            for impl in ("hip", "torch")}
+            for impl in ("hip", "torch") + (("mfma",) if args.mfma else ())}
     for row in args.rows.split(","):
         B, S = (int(x) for x in row.split("x"))
         ids = torch.randint(0, cfg.vocab, (B, S),
@@ -86,7 +92,8 @@ def main():
                     lambda: g.generate(ids, max_new_tokens=args.new))
                 if r:
                     times[impl].append((tn - t1) / (args.new - 1) * 1e3)
-        res = {"bench": "generate", "layers": cfg.n_layer, "H": 32, "Hkv": 8,
+        res = {"bench": "generate", "layers": cfg.n_layer, "H": 32,
+               "Hkv": args.kv_heads,
                "D": 128, "B": B, "prompt": S, "new": args.new,
                "tokens_equal_frac": round(
                    (outs["hip"] == outs["torch"]).float().mean().item(), 4)}
@@ -97,6 +104,10 @@ def main():
         res["torch_over_hip"] = round(
             statistics.median(times["torch"])
             / statistics.median(times["hip"]), 2)
+        if args.mfma:
+            res["hip_over_mfma"] = round(
+                statistics.median(times["hip"])
+                / statistics.median(times["mfma"]), 3)
         print(json.dumps(res), flush=True)
 
 
