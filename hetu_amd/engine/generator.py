@@ -55,11 +55,25 @@ def sample_next(logits: torch.Tensor, temperature: float = 0.0,
 
 class LlamaKVCache:
     def __init__(self, cfg: LlamaConfig, batch: int, max_len: int,
-                 device, dtype):
+                 device, dtype, kv_dtype: Optional[str] = None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got "
+                             f"{kv_dtype!r}")
         dh = cfg.hidden // cfg.n_head
         shape = (cfg.n_layer, batch, cfg.n_kv_head, max_len, dh)
-        self.k = torch.zeros(shape, device=device, dtype=dtype)
-        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        self.kv_dtype = kv_dtype
+        if kv_dtype == "fp8":
+            # e4m3 codes and one fp32 scale per cached row (token x KV
+            # head): value = float(code) * scale[row]
+            self.k = torch.zeros(shape, device=device,
+                                 dtype=torch.float8_e4m3fn)
+            self.v = torch.zeros_like(self.k)
+            self.k_scale = torch.zeros(shape[:-1], device=device,
+                                       dtype=torch.float32)
+            self.v_scale = torch.zeros_like(self.k_scale)
+        else:
+            self.k = torch.zeros(shape, device=device, dtype=dtype)
+            self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.len = 0
         # rows of the cache a decode step attends, the new token's included
         # (pos0 + 1), for the GPU decode kernel.  generate() advances it in
@@ -72,10 +86,13 @@ class LlamaGenerator:
     def __init__(self, cfg: LlamaConfig, state: Dict[str, torch.Tensor],
                  device: Optional[torch.device] = None,
                  dtype: torch.dtype = torch.float32,
-                 decode_impl: Optional[str] = None):
+                 decode_impl: Optional[str] = None,
+                 kv_dtype: Optional[str] = None):
         self.cfg = cfg
         # forwarded to F.flash_attn_decode: None (auto), "torch" or "hip"
         self.decode_impl = decode_impl
+        # None: the cache holds `dtype`; "fp8": e4m3 with per-row scales
+        self.kv_dtype = kv_dtype
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() else "cpu")
         self.dtype = dtype
@@ -122,20 +139,42 @@ class LlamaGenerator:
         q = F.rope_fwd(q, cos, sin)
         k = F.rope_fwd(k, cos, sin)
         v = v.view(B, S, Hkv, dh)
-        # append to cache
-        cache.k[layer][:, :, pos0:pos0 + S] = k.permute(0, 2, 1, 3)
-        cache.v[layer][:, :, pos0:pos0 + S] = v.permute(0, 2, 1, 3)
-        kk = cache.k[layer][:, :, :pos0 + S]
-        vv = cache.v[layer][:, :, :pos0 + S]
+        ks = vs = None
+        if cache.kv_dtype == "fp8":
+            # quantize into rows cache.kv_len - S + s: the device-side
+            # length, so append + decode attention hold no Python position
+            ks, vs = cache.k_scale[layer], cache.v_scale[layer]
+            F.kv_cache_append_fp8(
+                k, v, cache.k[layer], cache.v[layer], ks, vs, cache.kv_len,
+                impl=None if k.dtype == torch.bfloat16 else "torch")
+            if S == 1:
+                kk = vv = None
+            elif pos0 == 0:
+                # prefill attends the rows it just computed
+                kk, vv = k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3)
+            else:
+                # cold path: the visible slice, dequantized with torch
+                n = pos0 + S
+                kk = (cache.k[layer][:, :, :n].float()
+                      * ks[:, :, :n, None]).to(x.dtype)
+                vv = (cache.v[layer][:, :, :n].float()
+                      * vs[:, :, :n, None]).to(x.dtype)
+        else:
+            # append to cache
+            cache.k[layer][:, :, pos0:pos0 + S] = k.permute(0, 2, 1, 3)
+            cache.v[layer][:, :, pos0:pos0 + S] = v.permute(0, 2, 1, 3)
+            kk = cache.k[layer][:, :, :pos0 + S]
+            vv = cache.v[layer][:, :, :pos0 + S]
         if S == 1:
             # the whole layer cache and the length: nothing is sliced, cast
             # or repeated here
             kc, vc = cache.k[layer], cache.v[layer]
             on_hip = F.flash_attn_decode_on_hip(q[:, 0], kc, vc,
-                                                impl=self.decode_impl)
+                                                impl=self.decode_impl,
+                                                k_scale=ks, v_scale=vs)
             o, _ = F.flash_attn_decode(
                 q[:, 0], kc, vc, cache.kv_len if on_hip else pos0 + 1,
-                self.scale, impl=self.decode_impl)
+                self.scale, impl=self.decode_impl, k_scale=ks, v_scale=vs)
             return o.reshape(B, 1, H * dh) \
                 @ self.w[f"l{layer}.attn.wo.weight"].t()
         qt = q.permute(0, 2, 1, 3)
@@ -189,7 +228,7 @@ class LlamaGenerator:
         ids = input_ids.to(self.device)
         B, S = ids.shape
         cache = LlamaKVCache(self.cfg, B, S + max_new_tokens, self.device,
-                             self.dtype)
+                             self.dtype, kv_dtype=self.kv_dtype)
         gen = torch.Generator(device="cpu").manual_seed(seed)
         cache.kv_len.fill_(S)
         logits = self._forward(ids, cache, 0)

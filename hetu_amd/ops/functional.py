@@ -671,8 +671,79 @@ def _decode_torch(q, k_cache, v_cache, kv_len, scale):
     return o.squeeze(2), lse.squeeze(-1)
 
 
-def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None) -> bool:
-    """Whether flash_attn_decode sends this call to the HIP kernel (with
+_FP8 = torch.float8_e4m3fn
+
+
+def _decode_is_fp8(k_cache, v_cache, k_scale, v_scale) -> bool:
+    """Whether the caches are the fp8 format (e4m3 codes, one fp32 scale per
+    cached row: value = float(code) * scale[row]); checks that caches and
+    scales go together."""
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype == torch.uint8:
+            raise RuntimeError(
+                f"flash_attn_decode: {name} is uint8; pass the codes as "
+                f"{name}.view(torch.float8_e4m3fn)")
+    scales = (("k_scale", k_scale, k_cache), ("v_scale", v_scale, v_cache))
+    if k_cache.dtype != _FP8 and v_cache.dtype != _FP8:
+        for name, t, _ in scales:
+            if t is not None:
+                raise RuntimeError(
+                    f"flash_attn_decode: {name} given with a "
+                    f"{k_cache.dtype} cache; scales belong to fp8 caches")
+        return False
+    if k_cache.dtype != v_cache.dtype:
+        raise RuntimeError("flash_attn_decode: k_cache and v_cache must "
+                           "both be float8_e4m3fn")
+    for name, t, cache in scales:
+        if t is None:
+            raise RuntimeError(f"flash_attn_decode: an fp8 cache needs "
+                               f"{name} (fp32 [B, Hkv, L])")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"flash_attn_decode: {name} is {t.dtype}, "
+                               "not float32")
+        if tuple(t.shape) != tuple(cache.shape[:3]):
+            raise RuntimeError(
+                f"flash_attn_decode: {name} has shape {tuple(t.shape)}, "
+                f"need [B, Hkv, L] = {tuple(cache.shape[:3])}")
+    return True
+
+
+def _decode_fp8_ineligible(q, k_cache, v_cache, k_scale, v_scale,
+                           kv_len) -> Optional[str]:
+    """Why ops/hip/attention_decode_fp8.hip cannot take this input, or
+    None."""
+    ts = (("q", q), ("k_cache", k_cache), ("v_cache", v_cache),
+          ("k_scale", k_scale), ("v_scale", v_scale))
+    for name, t in ts:
+        if not t.is_cuda:
+            return f"{name} is not on the GPU"
+    if q.dtype != torch.bfloat16:
+        return f"q is {q.dtype}, not bf16"
+    if q.shape[-1] not in (64, 128):
+        return f"head dim {q.shape[-1]} is not 64 or 128"
+    if k_cache.shape[1] < 1 or q.shape[1] % k_cache.shape[1]:
+        return (f"H ({q.shape[1]}) is not a multiple of Hkv "
+                f"({k_cache.shape[1]})")
+    if isinstance(kv_len, torch.Tensor):
+        if not kv_len.is_cuda:
+            return "kv_len is a CPU tensor (pass an int or a device tensor)"
+        if kv_len.dtype != torch.int32:
+            return f"kv_len is {kv_len.dtype}, not int32"
+    for name, t in ts:
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            return f"{name} has a non-unit last stride"
+    # q in 8-element (16-byte) steps, the code bytes in 16-byte steps
+    for name, t, step in (("q", q, 8), ("k_cache", k_cache, 16),
+                          ("v_cache", v_cache, 16)):
+        if any(s % step for s, n in zip(t.stride()[:-1], t.shape) if n > 1) \
+                or t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned in every stride"
+    return None
+
+
+def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None,
+                             k_scale=None, v_scale=None) -> bool:
+    """Whether flash_attn_decode sends this call to a HIP kernel (with
     impl="hip" always: an ineligible input is then an error there).  The
     generators ask before they choose between the device length tensor and
     the Python int, which keeps the torch branch on its slicing form."""
@@ -680,6 +751,13 @@ def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None) -> bool:
         return False
     if impl in ("hip", "mfma"):
         return True
+    if k_scale is not None or k_cache.dtype in (_FP8, torch.uint8):
+        # the one HIP kernel for the dtype; no row of
+        # profiles/r10_decode_fp8.md has the torch branch ahead of it
+        return (_decode_is_fp8(k_cache, v_cache, k_scale, v_scale)
+                and _decode_fp8_ineligible(q, k_cache, v_cache, k_scale,
+                                           v_scale, kv_len) is None
+                and "fa" not in _TORCH_FB)
     return (_decode_hip_ineligible(q, k_cache, v_cache, kv_len) is None
             and "fa" not in _TORCH_FB
             and _decode_auto_hip(q.shape[0], k_cache.shape[1],
@@ -687,7 +765,8 @@ def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None) -> bool:
 
 
 def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
-                      num_splits: int = 0, impl=None):
+                      num_splits: int = 0, impl=None, k_scale=None,
+                      v_scale=None):
     """Attention of ONE new token per sequence over a KV cache.
 
     q [B, H, D]; k_cache, v_cache [B, Hkv, L, D] (H % Hkv == 0), taken with
@@ -699,27 +778,41 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
     exp(scale * q.k_j), the definition flash_attn_fwd uses); kv_len == 0
     gives out = 0, lse = -inf.
 
+    fp8 caches: k_cache / v_cache of dtype torch.float8_e4m3fn with k_scale,
+    v_scale fp32 [B, Hkv, L], one scale per cached row; an element's value
+    is float(code) * scale[row] (kv_cache_append_fp8 writes the format) and
+    out, lse are those of the dequantized values.  bf16 caches take no
+    scales.  Scales past kv_len may hold anything as well.
+
     impl: "hip" = the split-KV VALU kernel (bf16, D 64 or 128, GPU; an error
     on anything else, never a fallback); "mfma" = the MFMA kernel for wide
     GQA groups and MQA, same contract and eligibility, any H / Hkv; "torch" =
     fp32 torch math; None = a kernel where one is eligible and measured
     ahead (the MFMA one where _decode_auto_mfma says so, HETU_AMD_DECODE=
-    hip|mfma|auto overrides that choice), else torch.  num_splits
-    (HIP only): 0 lets the launcher choose from B, Hkv, L and the CU count
-    (never from the values of kv_len, so a captured graph stays valid);
-    >= 1 forces it."""
+    hip|mfma|auto overrides that choice), else torch.  An fp8 cache has one
+    HIP kernel (ops/hip/attention_decode_fp8.hip), which None, "hip" and
+    "mfma" all reach.  num_splits (HIP only): 0 lets the launcher choose
+    from B, Hkv, L and the CU count (never from the values of kv_len, so a
+    captured graph stays valid); >= 1 forces it."""
     if impl not in _DECODE_IMPLS:
         raise ValueError("flash_attn_decode: impl must be None, 'torch', "
                          f"'hip' or 'mfma', got {impl!r}")
     _decode_check_shapes(q, k_cache, v_cache)
+    fp8 = _decode_is_fp8(k_cache, v_cache, k_scale, v_scale)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if not flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len, impl):
+    if not flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len, impl,
+                                    k_scale, v_scale):
+        if fp8:
+            k_cache = k_cache.float() * k_scale.unsqueeze(-1)
+            v_cache = v_cache.float() * v_scale.unsqueeze(-1)
         return _decode_torch(q, k_cache, v_cache, kv_len, scale)
-    why = _decode_hip_ineligible(q, k_cache, v_cache, kv_len)
+    why = _decode_fp8_ineligible(q, k_cache, v_cache, k_scale, v_scale,
+                                 kv_len) if fp8 \
+        else _decode_hip_ineligible(q, k_cache, v_cache, kv_len)
     if why is not None:
         raise RuntimeError(f"flash_attn_decode(impl={impl!r}): {why}")
-    if impl is None:
+    if impl is None and not fp8:
         impl = _decode_env()
         if impl == "auto":
             impl = "mfma" if _decode_auto_mfma(
@@ -730,11 +823,88 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
         n = min(max(int(kv_len), 0), k_cache.shape[2])
         kv_len = torch.full((q.shape[0],), n, dtype=torch.int32,
                             device=q.device)
+    if fp8:
+        out, lse = ext().flash_attn_decode_fp8(
+            q, k_cache, v_cache, k_scale, v_scale, kv_len, float(scale),
+            int(num_splits))
+        return out, lse
     kernel = ext().flash_attn_decode_mfma if impl == "mfma" \
         else ext().flash_attn_decode
     out, lse = kernel(q, k_cache, v_cache, kv_len, float(scale),
                       int(num_splits))
     return out, lse
+
+
+def _kv_append_fp8_torch(k_new, v_new, k_cache, v_cache, k_scale, v_scale,
+                         end):
+    """kv_cache_append_fp8 in torch ops, the same definition."""
+    B, S, Hkv, D = k_new.shape
+    L = k_cache.shape[2]
+    dev = k_new.device
+    tgt = end.to(dev).long().view(B, 1) - S + torch.arange(S, device=dev)
+    bi, si = torch.nonzero((tgt >= 0) & (tgt < L), as_tuple=True)
+    ri = tgt[bi, si]
+    for x, cache, sc in ((k_new, k_cache, k_scale), (v_new, v_cache, v_scale)):
+        xf = x[bi, si].float()                              # [n, Hkv, D]
+        amax = xf.abs().amax(-1)
+        # a tensor divisor: IEEE division, never a reciprocal multiply
+        s = amax / torch.full_like(amax, 448.0)
+        y = torch.where(s.unsqueeze(-1) == 0, torch.zeros_like(xf),
+                        (xf / s.unsqueeze(-1)).clamp(-448.0, 448.0))
+        cache[bi, :, ri] = y.to(_FP8)
+        sc[bi, :, ri] = s
+
+
+def kv_cache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale,
+                        end, impl=None):
+    """Quantize new K / V rows into an fp8 KV cache, in place.
+
+    k_new, v_new [B, S, Hkv, D] bf16, taken with their strides (views into
+    a fused qkv output are read in place); k_cache, v_cache [B, Hkv, L, D]
+    torch.float8_e4m3fn and k_scale, v_scale [B, Hkv, L] fp32, with their
+    strides too (a layer slice is written in place); end int32 [B]: the
+    length AFTER the append, so row s of batch b goes to cache row
+    end[b] - S + s.  Rows outside [0, L) are dropped.
+
+    Per cached row: scale = amax(|x|) / 448 in fp32 (0 for a row of zeros)
+    and code = e4m3(clamp(x / scale, -448, 448)), round to nearest even, so
+    an element's value is float(code) * scale[row].  Non-finite input rows
+    give unspecified codes.
+
+    impl: "hip" = ops/hip/kv_cache_fp8.hip, one launch for K and V with the
+    row index read on the device (no host sync: capturable); "torch" = the
+    same definition in torch ops; None = the kernel on the GPU, else torch
+    (and with HETU_AMD_TORCH_FALLBACK=fa)."""
+    if impl not in (None, "torch", "hip"):
+        raise ValueError("kv_cache_append_fp8: impl must be None, 'torch' "
+                         f"or 'hip', got {impl!r}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype == torch.uint8:
+            raise RuntimeError(
+                f"kv_cache_append_fp8: {name} is uint8; pass the codes as "
+                f"{name}.view(torch.float8_e4m3fn)")
+        if t.dtype != _FP8:
+            raise RuntimeError(f"kv_cache_append_fp8: {name} is {t.dtype}, "
+                               "not float8_e4m3fn")
+    if k_new.dim() != 4 or k_new.shape != v_new.shape or k_cache.dim() != 4 \
+            or k_cache.shape != v_cache.shape \
+            or k_cache.shape[:2] != (k_new.shape[0], k_new.shape[2]) \
+            or k_cache.shape[3] != k_new.shape[3] \
+            or tuple(k_scale.shape) != tuple(k_cache.shape[:3]) \
+            or tuple(v_scale.shape) != tuple(k_cache.shape[:3]):
+        raise ValueError(
+            "kv_cache_append_fp8: need k_new, v_new [B, S, Hkv, D], caches "
+            "[B, Hkv, L, D] and scales [B, Hkv, L]; got "
+            f"{tuple(k_new.shape)}, {tuple(v_new.shape)}, "
+            f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}, "
+            f"{tuple(k_scale.shape)}, {tuple(v_scale.shape)}")
+    if impl is None:
+        impl = "hip" if k_new.is_cuda and "fa" not in _TORCH_FB else "torch"
+    if impl == "torch":
+        return _kv_append_fp8_torch(k_new, v_new, k_cache, v_cache, k_scale,
+                                    v_scale, end)
+    ext().kv_cache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale,
+                              v_scale, end)
 
 
 # ---------------------------------------------------------------------------

@@ -159,6 +159,17 @@ std::vector<torch::Tensor> flash_attn_decode_mfma(torch::Tensor q,
                                                   torch::Tensor kv_len,
                                                   double scale,
                                                   int64_t num_splits);
+// attention_decode_fp8.hip
+int64_t decode_attn_fp8_tile();
+std::vector<torch::Tensor> flash_attn_decode_fp8(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor kv_len,
+    double scale, int64_t num_splits);
+// kv_cache_fp8.hip
+void kv_cache_append_fp8(torch::Tensor k_new, torch::Tensor v_new,
+                         torch::Tensor k_cache, torch::Tensor v_cache,
+                         torch::Tensor k_scale, torch::Tensor v_scale,
+                         torch::Tensor end);
 
 // embed_cache.cpp
 void register_embed_cache(pybind11::module& m);
@@ -235,4 +246,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_decode_mfma", &flash_attn_decode_mfma, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
         py::arg("scale"), py::arg("num_splits") = 0);
+  m.def("decode_attn_fp8_tile", &decode_attn_fp8_tile);
+  m.def("flash_attn_decode_fp8", &flash_attn_decode_fp8, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"),
+        py::arg("num_splits") = 0);
+  m.def("kv_cache_append_fp8", &kv_cache_append_fp8);
 }

@@ -34,6 +34,8 @@ SOURCES = [
     "attention_bwd_v2.hip",
     "attention_decode.hip",
     "attention_decode_mfma.hip",
+    "attention_decode_fp8.hip",
+    "kv_cache_fp8.hip",
     "quant.hip",
     "moe.hip",
     "ltgemm.cpp",
@@ -46,9 +48,11 @@ SOURCES = [
 # per-source extra flags.  New kernels are compiled without the packed fp32
 # VALU ops (v_pk_{add,mul,fma}_f32); the older sources keep the code
 # generation they were measured with.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "attention_decode_mfma.hip": ["-Xclang", "-target-feature", "-Xclang",
-                                  "-packed-fp32-ops"],
+    "attention_decode_mfma.hip": _NO_PK_F32,
+    "attention_decode_fp8.hip": _NO_PK_F32,
+    "kv_cache_fp8.hip": _NO_PK_F32,
 }
 
 
