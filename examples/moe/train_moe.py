@@ -9,6 +9,8 @@ Set HETU_AMD_MOE_NODE_SIZE to enable the 3-phase hierarchical a2a.
 --aux-coef A / --z-coef Z add A * (load-balance loss) + Z * (router z-loss)
 to the training loss (the fused gate, ht.moe_gate) and print both with the
 largest expert's share of this rank's token choices every 10 steps.
+--expert-gemm grouped runs the expert GEMMs through ht.grouped_matmul (the
+hand-written grouped kernels on bf16 GPU inputs) instead of the padded bmm.
 """
 import argparse
 import os
@@ -32,6 +34,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--aux-coef", type=float, default=0.0)
     ap.add_argument("--z-coef", type=float, default=0.0)
+    ap.add_argument("--expert-gemm", choices=("bmm", "grouped"),
+                    default="bmm")
     args = ap.parse_args()
     gate_losses = bool(args.aux_coef or args.z_coef)
     comm = comm_backend()
@@ -48,7 +52,8 @@ def main():
                              ds=spec.ds_tokens(0) if spec else None,
                              device_group=spec.device_group if spec else None)
         moe = MoEMLP(H, F, E, spec=spec, k=2, gate_type="topk",
-                     aux_loss_coef=args.aux_coef, z_loss_coef=args.z_coef)
+                     aux_loss_coef=args.aux_coef, z_loss_coef=args.z_coef,
+                     expert_gemm=args.expert_gemm)
         loss = ht.mse_loss(moe(x), tgt)
         fetches = []
         if gate_losses:

@@ -341,6 +341,15 @@ def moe_gate(logits, k: int):
     return op.output(0), op.output(1), op.output(2)
 
 
+def grouped_matmul(a, b, counts, seg: int):
+    """a [G, M, K] @ b [G, K, N] per group with the empty slot rows zero:
+    counts [G, P] int32 filled slots per segment of seg rows, M = P * seg
+    (the expert GEMM of a MoE block; see ops.functional.grouped_gemm)."""
+    from .moe_ops import GroupedMatMulOp
+    return _cg().make_op(GroupedMatMulOp(), [_ac(a), _ac(b), counts],
+                         {"seg": int(seg), "trans_b": False}).output()
+
+
 _DROPOUT_SEED = [12345]
 _DROPOUT_OFFSET = [0]
 

@@ -289,3 +289,78 @@ class MoEGateGradOp(OpInterface):
                                for h in op.attrs["has"]]
         logits, lse, cnt = inputs[-3:]
         return [F.moe_gate_grad(g_probs, g_aux, g_z, logits, lse, cnt)]
+
+
+class MoESlotCountsOp(OpInterface):
+    """inputs: pos [E, C] -> counts [El, P] int32: counts[e, s] is the number
+    of filled slots in segment s (the rows from source rank s) of local
+    expert e in the [El, P*C, h] buffers, i.e. what ht.grouped_matmul takes.
+    For P > 1 the per-source counts travel as expert_in does: a2a by
+    destination rank, then [P, El] -> [El, P].  No gradient."""
+    type = "MoESlotCounts"
+
+    def infer_meta(self, attrs, inputs):
+        P = len(attrs.get("ep_ranks") or [0])
+        return [TensorMeta([attrs["experts"] // P, P], torch.int32)]
+
+    def deduce_states(self, op):
+        pos = op.inputs[0]
+        op.outputs[0].ds = pos.ds
+        op.outputs[0].device_group = pos.device_group
+
+    def compute(self, op, inputs, ctx):
+        ranks = _ep_ranks(op, ctx)
+        P = len(ranks)
+        El = op.attrs["experts"] // P
+        counts = F.moe_slot_counts(inputs[0])             # [E] by destination
+        if P > 1:
+            counts = _a2a(ctx.comm, ranks, counts).reshape(P, El).t() \
+                .contiguous()
+        return [counts.reshape(El, P)]
+
+
+class GroupedMatMulOp(OpInterface):
+    """inputs: a [G, M, K], b ([G, K, N], or [G, N, K] with attrs["trans_b"]),
+    counts [G, P] int32 -> a @ b (or a @ b^T) with the rows that are empty
+    slots exactly zero (ops.functional.grouped_gemm); M = P * attrs["seg"].
+    The weight gradient a^T @ gy runs over all M rows without the counts: the
+    empty slot rows of a must hold zeros, as MoEDispatch and an earlier
+    GroupedMatMul (+ gelu) leave them."""
+    type = "GroupedMatMul"
+
+    def infer_meta(self, attrs, inputs):
+        a, b = inputs[0], inputs[1]
+        n = b.shape[-2] if attrs.get("trans_b") else b.shape[-1]
+        return [TensorMeta(list(a.shape[:-1]) + [n], a.dtype)]
+
+    def compute(self, op, inputs, ctx):
+        a, b, counts = inputs
+        return [F.grouped_gemm(a.contiguous(), b.contiguous(), counts,
+                               op.attrs["seg"],
+                               bool(op.attrs.get("trans_b")))]
+
+    def gradient(self, op, g):
+        if op.attrs.get("trans_b"):
+            raise NotImplementedError(
+                "GroupedMatMul: no gradient of the trans_b form")
+        gr = _g(op.outputs[0])
+        a, b, counts = op.inputs
+        gy = g[0]
+        da = _make(gr, GroupedMatMulOp(), [gy, b, counts],
+                   {"seg": op.attrs["seg"], "trans_b": True}).output()
+        db = _make(gr, GroupedMatMulTNOp(), [a, gy], {}).output()
+        return [da, db, None]
+
+
+class GroupedMatMulTNOp(OpInterface):
+    """inputs: a [G, M, K1], b [G, M, N] -> a^T @ b [G, K1, N], the weight
+    gradient of GroupedMatMul (ops.functional.grouped_gemm_tn)."""
+    type = "GroupedMatMulTN"
+
+    def infer_meta(self, attrs, inputs):
+        a, b = inputs
+        return [TensorMeta([a.shape[0], a.shape[-1], b.shape[-1]], a.dtype)]
+
+    def compute(self, op, inputs, ctx):
+        a, b = inputs
+        return [F.grouped_gemm_tn(a.contiguous(), b.contiguous())]

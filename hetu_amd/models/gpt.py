@@ -49,6 +49,9 @@ class GPTConfig:
     # over the MoE layers and added to the LM loss (0 = plain softmax gate)
     moe_aux_coef: float = 0.0
     moe_z_coef: float = 0.0
+    # how the expert GEMMs run: "bmm" (padded batched matmul) or "grouped"
+    # (ht.grouped_matmul, skips the empty slots)
+    moe_expert_gemm: str = "bmm"
 
 
 GPT_CONFIGS = {
@@ -159,7 +162,8 @@ class GPTMoEMLP(Module):
                           k=cfg.moe_k, capacity_factor=cfg.moe_capacity,
                           dtype=dtype, name=f"h{layer_idx}.moe",
                           aux_loss_coef=cfg.moe_aux_coef,
-                          z_loss_coef=cfg.moe_z_coef)
+                          z_loss_coef=cfg.moe_z_coef,
+                          expert_gemm=cfg.moe_expert_gemm)
         self.hidden = cfg.hidden
 
     def forward(self, x):

@@ -12,7 +12,8 @@ from typing import List, Optional
 import torch
 
 from ..graph.ops import api as ht
-from ..graph.ops.moe_ops import MoECombineOp, MoEDispatchOp
+from ..graph.ops.moe_ops import (MoECombineOp, MoEDispatchOp,
+                                 MoESlotCountsOp)
 from ..graph.ops.basics import _make
 from . import init
 from .module import Module
@@ -39,6 +40,10 @@ class MoEMLP(Module):
     plain softmax path), self.gate_counts the per-expert choice counts.  The layer does not add them to anything: the
     model weighs them with the coefficients.  fused_gate forces the choice
     (None = fused iff a coefficient is non-zero).
+
+    expert_gemm: "bmm" runs the two expert GEMMs as padded batched matmuls
+    (ht.bmm); "grouped" as ht.grouped_matmul, which takes the per-expert
+    slot counts and skips the empty slots, forward and backward.
     """
 
     def __init__(self, hidden: int, ffn_hidden: int, num_experts: int,
@@ -46,8 +51,13 @@ class MoEMLP(Module):
                  capacity_factor: float = 1.25, dtype=torch.float32,
                  gate_type: str = "topk", name: str = "moe",
                  aux_loss_coef: float = 0.0, z_loss_coef: float = 0.0,
-                 fused_gate: Optional[bool] = None):
+                 fused_gate: Optional[bool] = None,
+                 expert_gemm: str = "bmm"):
         super().__init__()
+        if expert_gemm not in ("bmm", "grouped"):
+            raise ValueError(f"expert_gemm must be 'bmm' or 'grouped', got "
+                             f"{expert_gemm!r}")
+        self.expert_gemm = expert_gemm
         spec = spec or ParallelSpec()
         self.spec = spec
         self.E = num_experts
@@ -139,9 +149,16 @@ class MoEMLP(Module):
         disp = _make(g, MoEDispatchOp(), [x, probs], dict(attrs),
                      name="moe_dispatch")
         expert_in, wk, pos, slot_of = disp.outputs
-        h1 = ht.bmm(expert_in, self.w1)           # [El, P*C, f]
-        h1 = ht.gelu(h1)
-        eo = ht.bmm(h1, self.w2)                  # [El, P*C, h]
+        if self.expert_gemm == "grouped":
+            counts = _make(g, MoESlotCountsOp(), [pos], dict(attrs),
+                           name="moe_slot_counts").output()   # [El, P]
+            h1 = ht.grouped_matmul(expert_in, self.w1, counts, C)
+            h1 = ht.gelu(h1)
+            eo = ht.grouped_matmul(h1, self.w2, counts, C)
+        else:
+            h1 = ht.bmm(expert_in, self.w1)       # [El, P*C, f]
+            h1 = ht.gelu(h1)
+            eo = ht.bmm(h1, self.w2)              # [El, P*C, h]
         attrs["out_ds"] = x.ds
         y = _make(g, MoECombineOp(), [eo, wk, pos, slot_of], dict(attrs),
                   name="moe_combine").output()

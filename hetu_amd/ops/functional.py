@@ -67,7 +67,7 @@ def _gpu(*ts) -> bool:
 # Debug bisect switch: HETU_AMD_TORCH_FALLBACK="fa,ln,adam,..." routes the
 # named kernel families to the plain-torch reference implementations even
 # on GPU (they are device-agnostic).  Families: fa, qkvfa, ln, rms, gelu,
-# silu, swiglu, adam, ce, vce, embed, softmax, rope, dropout, moe.
+# silu, swiglu, adam, ce, vce, embed, softmax, rope, dropout, moe, gmm.
 _TORCH_FB = frozenset(
     s for s in os.environ.get("HETU_AMD_TORCH_FALLBACK", "").split(",") if s)
 
@@ -1670,3 +1670,169 @@ def moe_gate_grad(g_probs: Optional[torch.Tensor],
     if g_z is not None:
         dl = dl + (g_z.float().reshape(()) * (2.0 / N)) * l * p
     return dl.to(logits.dtype)
+
+
+# ---------------------------------------------------------------------------
+# Grouped expert GEMMs (ops/hip/gemm_grouped.hip, gemm_wgrad.hip): the three
+# GEMM forms of a MoE expert block over the [G, M, K] slot buffers, each
+# operand read where it lies.  M = P * seg rows per group: P segments of seg
+# slots, segment s of group g filled as a prefix of counts[g, s] rows; row r
+# is valid iff (r % seg) < counts[g, r // seg].  Invalid output rows are
+# exactly zero on both branches and invalid input rows reach no valid row.
+# The torch branch (matmul, then the zeroing) serves CPU, other dtypes,
+# ineligible shapes and HETU_AMD_TORCH_FALLBACK=gmm.
+# ---------------------------------------------------------------------------
+
+# N tile of the hand kernel (128 or 256): the eligibility rule and the tile
+# the launch uses
+GMM_N_TILE = 128
+_GMM_IMPLS = (None, "hip", "torch")
+
+
+def _gmm_row_mask(counts, G: int, M: int, seg: int, device):
+    """[G, M] bool: which rows are filled slots."""
+    P = M // seg
+    q = torch.arange(seg, device=device).view(1, 1, seg)
+    return (q < counts.to(device).view(G, P, 1)).reshape(G, M)
+
+
+def _gmm_transposed(t):
+    """t^T per group for the torch branch.  On a GPU the transpose is
+    materialised, as BatchMatMulTNOp does: the library's strided-batched
+    NT / TN kernels over-read their transposed operand."""
+    t = t.transpose(1, 2)
+    return t.contiguous() if t.is_cuda else t
+
+
+def _gmm_check_counts(a, counts, seg):
+    """Shape contract of (counts, seg), the same on both branches."""
+    G, M = a.shape[0], a.shape[1]
+    if counts is None:
+        return
+    if counts.dim() != 2 or counts.shape[0] != G:
+        raise RuntimeError(f"grouped_gemm: counts must be [G, P] with G = {G}"
+                           f", got {tuple(counts.shape)}")
+    if seg is None or seg < 1 or counts.shape[1] * seg != M:
+        raise RuntimeError(
+            f"grouped_gemm: counts has P = {counts.shape[1]} segments of "
+            f"seg = {seg} rows, a has M = {M} rows")
+
+
+def _gmm_hip_ineligible(a, b, counts, trans_b) -> Optional[str]:
+    """Why ops/hip/gemm_grouped.hip cannot take this input, or None."""
+    for name, t in (("a", a), ("b", b)):
+        if not t.is_cuda:
+            return f"{name} is not on the GPU"
+        if t.dtype != torch.bfloat16:
+            return f"{name} is {t.dtype}, not bf16"
+        if t.dim() != 3:
+            return f"{name} is not 3-D"
+        if not t.is_contiguous():
+            return f"{name} is not contiguous"
+        if t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned"
+    if b.device != a.device:
+        return f"b is on {b.device}, a on {a.device}"
+    K = a.shape[2]
+    N = b.shape[1] if trans_b else b.shape[2]
+    if a.shape[1] < 1:
+        return "a has no rows"
+    if K < 64 or K % 64:
+        return f"a has K = {K}, not a positive multiple of 64"
+    if N < GMM_N_TILE or N % GMM_N_TILE:
+        return (f"b has {N} output columns, not a positive multiple of "
+                f"{GMM_N_TILE}")
+    if counts is not None:
+        if counts.device != a.device:
+            return f"counts is on {counts.device}, a on {a.device}"
+        if counts.dtype != torch.int32:
+            return f"counts is {counts.dtype}, not int32"
+        if not counts.is_contiguous():
+            return "counts is not contiguous"
+    return None
+
+
+def grouped_gemm(a, b, counts=None, seg=None, trans_b: bool = False,
+                 impl=None):
+    """out [G, M, N] = a [G, M, K] @ b [G, K, N], or with trans_b
+    a @ b [G, N, K]^T, with every invalid row (see above) exactly zero.
+    counts: int32 [G, P] on a's device with P * seg == M, or None (all rows
+    valid).
+
+    impl: "hip" = the hand kernel, an error naming the argument if the input
+    is not eligible (never a fallback); "torch" = matmul + zeroing; None =
+    the hand kernel where it is eligible."""
+    if impl not in _GMM_IMPLS:
+        raise ValueError(f"grouped_gemm: impl must be one of {_GMM_IMPLS}, "
+                         f"got {impl!r}")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] \
+            or a.shape[2] != b.shape[2 if trans_b else 1]:
+        raise RuntimeError(f"grouped_gemm: a {tuple(a.shape)} and b "
+                           f"{tuple(b.shape)} do not match (trans_b="
+                           f"{trans_b})")
+    _gmm_check_counts(a, counts, seg)
+    why = _gmm_hip_ineligible(a, b, counts, trans_b)
+    if impl == "hip":
+        if why is not None:
+            raise RuntimeError(f"grouped_gemm(impl='hip'): {why}")
+        use_hip = True
+    else:
+        use_hip = impl is None and why is None and _use_hip("gmm", a)
+    if use_hip:
+        return ext().grouped_gemm_bf16(a, b, counts, 0 if seg is None else seg,
+                                       trans_b, GMM_N_TILE)
+    if trans_b:
+        b = _gmm_transposed(b)
+    out = torch.matmul(a, b)
+    if counts is not None:
+        G, M = a.shape[0], a.shape[1]
+        mask = _gmm_row_mask(counts, G, M, seg, a.device)
+        out = torch.where(mask.unsqueeze(-1), out, torch.zeros_like(out))
+    return out
+
+
+def _gmm_tn_hip_ineligible(a, b) -> Optional[str]:
+    for name, t in (("a", a), ("b", b)):
+        if t.dim() != 3:
+            return f"{name} is not 3-D"
+        if t.shape[0] > 65535:
+            return f"{name} has more than 65535 groups"
+        if not _wgrad_hip_eligible(t[0], t[0]):
+            return (f"{name} {tuple(t.shape)} {t.dtype} is not a contiguous "
+                    "bf16 GPU tensor with M % 64 == 0 and a last dim that is "
+                    "a multiple of 256")
+    if not a.is_contiguous() or not b.is_contiguous():
+        return "a or b is not contiguous"
+    if a.device != b.device:
+        return f"b is on {b.device}, a on {a.device}"
+    return None
+
+
+def grouped_gemm_tn(a, b, impl=None):
+    """out [G, K1, N] = a [G, M, K1]^T @ b [G, M, N]: the per-expert weight
+    gradient over all M rows (invalid rows are zero by grouped_gemm's
+    guarantee, so no counts are taken).  impl as for grouped_gemm; the hand
+    kernel is linear_wgrad's body per group."""
+    if impl not in _GMM_IMPLS:
+        raise ValueError(f"grouped_gemm_tn: impl must be one of {_GMM_IMPLS}"
+                         f", got {impl!r}")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[:2] != b.shape[:2]:
+        raise RuntimeError(f"grouped_gemm_tn: a {tuple(a.shape)} and b "
+                           f"{tuple(b.shape)} do not match")
+    why = _gmm_tn_hip_ineligible(a, b)
+    if impl == "hip":
+        if why is not None:
+            raise RuntimeError(f"grouped_gemm_tn(impl='hip'): {why}")
+        use_hip = True
+    else:
+        use_hip = impl is None and why is None and _use_hip("gmm", a)
+    if use_hip:
+        return ext().grouped_gemm_tn_bf16(a, b)
+    return torch.matmul(_gmm_transposed(a), b)
+
+
+def moe_slot_counts(pos: torch.Tensor) -> torch.Tensor:
+    """pos [E, C] int64 (-1 = empty slot) -> int32 [E] filled slots."""
+    if _use_hip("gmm", pos) and pos.numel() > 0:
+        return ext().moe_slot_counts(pos.contiguous())
+    return (pos >= 0).sum(1).to(torch.int32)

@@ -116,6 +116,13 @@ std::vector<torch::Tensor> flash_attn_varlen_bwd(
 // rope.hip
 void rope_qk_inplace(torch::Tensor qkv, torch::Tensor cs, torch::Tensor sn,
                      int64_t n_rot, int64_t D, int64_t sign);
+// gemm_grouped.hip (grouped_gemm_tn_bf16: gemm_wgrad.hip)
+torch::Tensor grouped_gemm_bf16(torch::Tensor a, torch::Tensor b,
+                                c10::optional<torch::Tensor> counts,
+                                int64_t seg, bool trans_b, int64_t n_tile);
+torch::Tensor grouped_gemm_tn_bf16(torch::Tensor a, torch::Tensor b);
+torch::Tensor moe_slot_counts(torch::Tensor pos);
+
 // moe.hip
 std::vector<torch::Tensor> moe_topk(torch::Tensor probs, int64_t K);
 std::vector<torch::Tensor> moe_assign_slots(torch::Tensor idx,
@@ -223,6 +230,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
   m.def("flash_attn_bwd_qkv", &flash_attn_bwd_qkv);
   m.def("rope_qk_inplace", &rope_qk_inplace);
+  m.def("grouped_gemm_bf16", &grouped_gemm_bf16);
+  m.def("grouped_gemm_tn_bf16", &grouped_gemm_tn_bf16);
+  m.def("moe_slot_counts", &moe_slot_counts);
   m.def("moe_topk", &moe_topk);
   m.def("moe_assign_slots", &moe_assign_slots);
   m.def("moe_dispatch_rows", &moe_dispatch_rows, pybind11::arg("x"),

@@ -27,6 +27,7 @@ SOURCES = [
     "adam.hip",
     "gemm.hip",
     "gemm_wgrad.hip",
+    "gemm_grouped.hip",
     "transpose.hip",
     "attention.hip",
     "attention_v2.hip",
@@ -53,6 +54,7 @@ EXTRA_FLAGS = {
     "attention_decode_mfma.hip": _NO_PK_F32,
     "attention_decode_fp8.hip": _NO_PK_F32,
     "kv_cache_fp8.hip": _NO_PK_F32,
+    "gemm_grouped.hip": _NO_PK_F32,
 }
 
 

@@ -365,6 +365,19 @@ __global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_bias_bf16_kernel(
     wg_body<false>(gy, x, dw, db, T, N, K, tn, tk, smem);
 }
 
+// batched form for the per-expert weight gradients: blockIdx.y picks the
+// group, the three pointers are offset to it and the body is the same
+__global__ __launch_bounds__(WG_THREADS) void gemm_wgrad_batched_bf16_kernel(
+    const bf16* __restrict__ gy, const bf16* __restrict__ x,
+    bf16* __restrict__ dw, int T, int N, int K, int tiles_n, int tiles_k) {
+  __shared__ __attribute__((aligned(1024))) char smem[WG_LDS];
+  int tn, tk;
+  wg_remap(tiles_n, tiles_k, tn, tk);
+  const int64_t grp = blockIdx.y;
+  wg_body<false>(gy + grp * T * N, x + grp * T * K, dw + grp * N * K, nullptr,
+                 T, N, K, tn, tk, smem);
+}
+
 // input check of the entry point; functional._wgrad_hip_eligible is the
 // routing rule and must not admit more than this
 bool wg_eligible(const torch::Tensor& gy, const torch::Tensor& x) {
@@ -416,4 +429,31 @@ std::vector<torch::Tensor> gemm_wgrad_bias_bf16(torch::Tensor gy,
                      (bf16*)dw.data_ptr(), (bf16*)db.data_ptr(), T, N, K,
                      tiles_n, tiles_k);
   return {dw, db};
+}
+
+// out [G, K1, N] = a [G, M, K1]^T @ b [G, M, N]: the per-expert weight
+// gradient, one launch; every group runs gemm_wgrad_bf16's body (gy := a,
+// x := b), so a group's result is bit-identical to gemm_wgrad_bf16's.
+torch::Tensor grouped_gemm_tn_bf16(torch::Tensor a, torch::Tensor b) {
+  const char* fn = "grouped_gemm_tn_bf16";
+  TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && a.size(0) == b.size(0) &&
+              a.size(0) >= 1 && a.size(0) <= 65535, fn,
+              ": a and b must be [G, M, K1] and [G, M, N] with 1 <= G <= "
+              "65535, got ", a.sizes(), " and ", b.sizes());
+  TORCH_CHECK(a.is_contiguous() && b.is_contiguous(), fn,
+              ": a and b must be contiguous");
+  TORCH_CHECK(wg_eligible(a[0], b[0]), fn,
+              " requires bf16 operands on one GPU: a [G, M, K1], b [G, M, N] "
+              "with K1 % 256 == 0, N % 256 == 0 and M % 64 == 0, got ",
+              a.sizes(), " ", a.scalar_type(), " and ", b.sizes(), " ",
+              b.scalar_type());
+  const int G = a.size(0), T = a.size(1), N = a.size(2), K = b.size(2);
+  auto dw = torch::empty({G, N, K}, b.options());
+  const int tiles_n = N / WG_TILE_MN, tiles_k = K / WG_TILE_MN;
+  hipLaunchKernelGGL(gemm_wgrad_batched_bf16_kernel,
+                     dim3(tiles_n * tiles_k, G), dim3(WG_THREADS), 0,
+                     hetu_current_stream(), (const bf16*)a.data_ptr(),
+                     (const bf16*)b.data_ptr(), (bf16*)dw.data_ptr(), T, N, K,
+                     tiles_n, tiles_k);
+  return dw;
 }
