@@ -82,12 +82,67 @@ class LlamaKVCache:
         self.kv_len = torch.zeros(batch, device=device, dtype=torch.int32)
 
 
+class PagedKVCache:
+    """A page pool per layer behind one block table.
+
+    k, v [n_layer, P, Hkv, PS, dh]; block_table int32 [B, MP]: key j of
+    sequence b is row j % PS of page block_table[b, j // PS]; kv_len int32
+    [B].  Sequence b owns ceil(capacity[b] / PS) pages, so P is the sum of
+    the sequences' own needs, not B x the longest.  Pages are handed out
+    round-robin over the sequences (physical order differs from logical
+    order); table entries a sequence does not own hold P, which the kernels
+    treat as a page of masked keys."""
+
+    def __init__(self, cfg: LlamaConfig, capacity, page_size: int, device,
+                 dtype):
+        if page_size not in F._PAGE_SIZES:
+            raise ValueError(f"page_size must be one of {F._PAGE_SIZES}, "
+                             f"got {page_size}")
+        dh = cfg.hidden // cfg.n_head
+        need = [-(-int(n) // page_size) for n in capacity]
+        self.page_size = page_size
+        self.num_pages = sum(need)
+        mp = max(need, default=0)
+        table = [[self.num_pages] * mp for _ in need]
+        nxt = 0
+        for j in range(mp):
+            for b, n in enumerate(need):
+                if j < n:
+                    table[b][j] = nxt
+                    nxt += 1
+        self.block_table = torch.tensor(table, dtype=torch.int32) \
+            .view(len(need), mp).to(device)
+        shape = (cfg.n_layer, self.num_pages, cfg.n_kv_head, page_size, dh)
+        self.k = torch.zeros(shape, device=device, dtype=dtype)
+        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        self.kv_len = torch.zeros(len(need), device=device, dtype=torch.int32)
+
+    def row(self, b: int) -> "PagedKVCache":
+        """Sequence b alone (B = 1) on the same pools, for its prefill."""
+        one = object.__new__(PagedKVCache)
+        one.__dict__.update(self.__dict__)
+        one.block_table = self.block_table[b:b + 1]
+        one.kv_len = self.kv_len[b:b + 1]
+        return one
+
+
 class LlamaGenerator:
     def __init__(self, cfg: LlamaConfig, state: Dict[str, torch.Tensor],
                  device: Optional[torch.device] = None,
                  dtype: torch.dtype = torch.float32,
                  decode_impl: Optional[str] = None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None,
+                 kv_layout: str = "dense", page_size: int = 64):
+        if kv_layout not in ("dense", "paged"):
+            raise ValueError(f"kv_layout must be 'dense' or 'paged', got "
+                             f"{kv_layout!r}")
+        if kv_layout == "paged" and kv_dtype is not None:
+            raise ValueError("kv_layout='paged' holds the model dtype; "
+                             "kv_dtype='fp8' is dense only")
+        # "paged": generate() keeps the cache in a PagedKVCache of page_size
+        # rows per page and also takes ragged prompts
+        self.kv_layout = kv_layout
+        self.page_size = page_size
         self.cfg = cfg
         # forwarded to F.flash_attn_decode: None (auto), "torch" or "hip"
         self.decode_impl = decode_impl
@@ -125,7 +180,45 @@ class LlamaGenerator:
         return cls(cfg, state, **kw)
 
     # ---- building blocks -------------------------------------------------
+    def _attn_paged(self, x, layer, cache: PagedKVCache):
+        """S > 1: the prefill of one sequence (cache = its row(), still
+        empty) on the rows it just computed; S == 1: a decode step of all
+        sequences.  cache.kv_len is the length after the append in both, and
+        positions, append and attention read it on the device."""
+        cfg = self.cfg
+        B, S, _ = x.shape
+        H, Hkv = cfg.n_head, cfg.n_kv_head
+        dh = cfg.hidden // H
+        qkv = x @ self.w[f"l{layer}.attn.wqkv.weight"].t()
+        q, k, v = qkv.split([H * dh, Hkv * dh, Hkv * dh], dim=-1)
+        q = q.view(B, S, H, dh)
+        k = k.view(B, S, Hkv, dh)
+        v = v.view(B, S, Hkv, dh)
+        kp, vp = cache.k[layer], cache.v[layer]
+        wo = self.w[f"l{layer}.attn.wo.weight"]
+        if S == 1:
+            # one RoPE row per sequence, gathered from its own position; the
+            # batch takes the place of the packed form's sequence dim
+            pos = (cache.kv_len - 1).long()
+            cos, sin = self.cos[pos], self.sin[pos]
+            q = F.rope_fwd(q[:, 0], cos, sin)
+            k = F.rope_fwd(k[:, 0], cos, sin).unsqueeze(1)
+            F.kv_cache_append_paged(k, v, kp, vp, cache.block_table,
+                                    cache.kv_len)
+            o, _ = F.flash_attn_decode(
+                q, kp, vp, cache.kv_len, self.scale, impl=self.decode_impl,
+                block_table=cache.block_table)
+            return o.reshape(B, 1, H * dh) @ wo.t()
+        q = F.rope_fwd(q, self.cos[:S], self.sin[:S])
+        k = F.rope_fwd(k, self.cos[:S], self.sin[:S])
+        F.kv_cache_append_paged(k, v, kp, vp, cache.block_table,
+                                cache.kv_len)
+        return self._prefill_attn(q, k.permute(0, 2, 1, 3),
+                                  v.permute(0, 2, 1, 3), 0) @ wo.t()
+
     def _attn(self, x, layer, cache: LlamaKVCache, pos0: int):
+        if isinstance(cache, PagedKVCache):
+            return self._attn_paged(x, layer, cache)
         cfg = self.cfg
         B, S, _ = x.shape
         H, Hkv = cfg.n_head, cfg.n_kv_head
@@ -177,6 +270,14 @@ class LlamaGenerator:
                 self.scale, impl=self.decode_impl, k_scale=ks, v_scale=vs)
             return o.reshape(B, 1, H * dh) \
                 @ self.w[f"l{layer}.attn.wo.weight"].t()
+        return self._prefill_attn(q, kk, vv, pos0) \
+            @ self.w[f"l{layer}.attn.wo.weight"].t()
+
+    def _prefill_attn(self, q, kk, vv, pos0):
+        """Causal attention of q [B, S, H, dh] at positions pos0 .. over kk,
+        vv [B, Hkv, pos0 + S, dh] -> [B, S, H * dh]."""
+        B, S, H, dh = q.shape
+        Hkv = kk.shape[1]
         qt = q.permute(0, 2, 1, 3)
         if qt.is_cuda and dh == 128 and qt.dtype == torch.bfloat16:
             o, _ = F.flash_attn_fwd(qt.contiguous(), kk.contiguous(),
@@ -189,15 +290,14 @@ class LlamaGenerator:
             if S > 1:
                 Skv = pos0 + S
                 mask = torch.ones(S, Skv, dtype=torch.bool,
-                                  device=x.device).tril(diagonal=Skv - S)
+                                  device=q.device).tril(diagonal=Skv - S)
             scores = (qt.float() @ kr.float().transpose(-1, -2)) \
                 * self.scale
             if mask is not None:
                 scores = scores.masked_fill(~mask, float("-inf"))
             p = torch.softmax(scores, dim=-1)
-            o = (p @ vr.float()).to(x.dtype)
-        o = o.permute(0, 2, 1, 3).reshape(B, S, H * dh)
-        return o @ self.w[f"l{layer}.attn.wo.weight"].t()
+            o = (p @ vr.float()).to(q.dtype)
+        return o.permute(0, 2, 1, 3).reshape(B, S, H * dh)
 
     def _block(self, x, layer, cache, pos0):
         cfg = self.cfg
@@ -224,7 +324,13 @@ class LlamaGenerator:
                  temperature: float = 0.0, top_k: int = 0,
                  top_p: float = 0.0, eos_id: Optional[int] = None,
                  seed: int = 0) -> torch.Tensor:
-        """input_ids [B, S] -> [B, S + new]; temperature 0 = greedy."""
+        """input_ids [B, S] -> [B, S + new]; temperature 0 = greedy.  With
+        kv_layout="paged" also a list of 1-D prompts of unequal length -> a
+        list of 1-D outputs, each cut after its first eos_id."""
+        if self.kv_layout == "paged":
+            return self._generate_paged(input_ids, max_new_tokens,
+                                        temperature, top_k, top_p, eos_id,
+                                        seed)
         ids = input_ids.to(self.device)
         B, S = ids.shape
         cache = LlamaKVCache(self.cfg, B, S + max_new_tokens, self.device,
@@ -246,6 +352,47 @@ class LlamaGenerator:
             logits = self._forward(nxt.unsqueeze(1), cache, pos)
             pos += 1
         return torch.cat(out, dim=1)
+
+
+    def _generate_paged(self, input_ids, max_new_tokens, temperature, top_k,
+                        top_p, eos_id, seed):
+        ragged = not isinstance(input_ids, torch.Tensor)
+        prompts = [p.to(self.device).view(-1) for p in input_ids]
+        lens = [int(p.numel()) for p in prompts]
+        B = len(prompts)
+        cache = PagedKVCache(self.cfg, [n + max_new_tokens for n in lens],
+                             self.page_size, self.device, self.dtype)
+        gen = torch.Generator(device="cpu").manual_seed(seed)
+        cache.kv_len.copy_(torch.tensor(lens, dtype=torch.int32))
+        # prefill: one sequence at a time through the dense prefill path
+        logits = torch.cat([self._forward(p.unsqueeze(0), cache.row(b), 0)
+                            for b, p in enumerate(prompts)])
+        new = []
+        alive = torch.ones(B, dtype=torch.bool)
+        for _ in range(max_new_tokens):
+            nxt = sample_next(logits, temperature, top_k, top_p, gen)
+            new.append(nxt.unsqueeze(1))
+            if eos_id is not None:
+                alive &= (nxt.cpu() != eos_id)
+                if not alive.any():
+                    break
+            # a finished sequence keeps stepping (the batch stays whole);
+            # its tokens past the eos are cut below
+            cache.kv_len.add_(1)
+            logits = self._forward(nxt.unsqueeze(1), cache, None)
+        new = torch.cat(new, dim=1) if new else \
+            torch.empty(B, 0, dtype=torch.long, device=self.device)
+        if not ragged:
+            return torch.cat([torch.stack(prompts), new], dim=1)
+        out = []
+        for b, p in enumerate(prompts):
+            row = new[b]
+            if eos_id is not None:
+                hit = (row == eos_id).nonzero()
+                if hit.numel():
+                    row = row[:int(hit[0]) + 1]
+            out.append(torch.cat([p, row]))
+        return out
 
 
 class GPTGenerator:

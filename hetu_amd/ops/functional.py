@@ -623,7 +623,25 @@ def _decode_env(switch=None) -> str:
     return switch
 
 
-def _decode_check_shapes(q, k_cache, v_cache):
+def _decode_check_shapes(q, k_cache, v_cache, block_table=None):
+    if block_table is not None:
+        # paged: pools [P, Hkv, PS, D] behind block_table [B, MP]
+        if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 \
+                or k_cache.shape != v_cache.shape \
+                or k_cache.shape[3] != q.shape[2]:
+            raise ValueError(
+                "flash_attn_decode: with a block_table need q [B, H, D] and "
+                f"k_cache, v_cache [P, Hkv, PS, D]; got {tuple(q.shape)}, "
+                f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+        if not isinstance(block_table, torch.Tensor) \
+                or block_table.dim() != 2 \
+                or block_table.shape[0] != q.shape[0] \
+                or block_table.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError(
+                "flash_attn_decode: block_table must be an integer tensor "
+                f"[B, MP] with B = {q.shape[0]}; got "
+                f"{tuple(getattr(block_table, 'shape', ()))}")
+        return
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 \
             or k_cache.shape != v_cache.shape \
             or k_cache.shape[0] != q.shape[0] \
@@ -634,12 +652,13 @@ def _decode_check_shapes(q, k_cache, v_cache):
             f"{tuple(v_cache.shape)}")
 
 
-def _decode_torch(q, k_cache, v_cache, kv_len, scale):
+def _decode_torch(q, k_cache, v_cache, kv_len, scale, keep_keys=None):
     """fp32 math on the given inputs, one rounding to q's dtype.  An int
     length slices the cache and repeats the KV heads, the composition the
     generators ran before the kernel existed (bit-identical to it); a
     tensor length masks, by selection: rows past kv_len[b] may hold
-    anything."""
+    anything.  keep_keys (bool [B, L], tensor length only) masks further
+    keys the same way."""
     B, H, D = q.shape
     Hkv, L = k_cache.shape[1], k_cache.shape[2]
     rep = H // Hkv
@@ -656,6 +675,8 @@ def _decode_torch(q, k_cache, v_cache, kv_len, scale):
         return o.squeeze(2), torch.logsumexp(scores, dim=-1).squeeze(-1)
     n = kv_len.to(q.device).clamp(0, L).view(B, 1, 1)
     valid = torch.arange(L, device=q.device).view(1, 1, L) < n   # [B, 1, L]
+    if keep_keys is not None:
+        valid = valid & keep_keys.view(B, 1, L)
     keep = valid.unsqueeze(-1)                                   # [B, 1, L, 1]
     kf = torch.where(keep, k_cache.float(), 0.0)
     vf = torch.where(keep, v_cache.float(), 0.0)
@@ -672,6 +693,104 @@ def _decode_torch(q, k_cache, v_cache, kv_len, scale):
 
 
 _FP8 = torch.float8_e4m3fn
+_PAGE_SIZES = (32, 64, 128, 256)
+
+
+def _decode_paged_ineligible(q, k_pool, v_pool, block_table,
+                             kv_len) -> Optional[str]:
+    """Why the paged HIP kernels (ops/hip/attention_decode_paged.hip, the
+    PAGED kernel of attention_decode_mfma.hip) cannot take this input, or
+    None."""
+    why = _decode_hip_ineligible(q, k_pool, v_pool, kv_len)
+    if why is not None:
+        return why
+    if k_pool.shape[2] not in _PAGE_SIZES:
+        return (f"the page size of k_cache / v_cache (dim 2) is "
+                f"{k_pool.shape[2]}, not one of {_PAGE_SIZES}")
+    if not block_table.is_cuda:
+        return "block_table is not on the GPU"
+    if block_table.dtype != torch.int32:
+        return f"block_table is {block_table.dtype}, not int32"
+    if not block_table.is_contiguous():
+        return "block_table is not contiguous"
+    return None
+
+
+def _decode_auto_paged_hip(B: int, Hkv: int, L: int) -> bool:
+    """Whether impl=None sends an eligible paged call to a paged kernel
+    rather than to the torch gather.  The gather copies every needed page
+    into a dense cache and then runs the fp32 composition that
+    _decode_auto_hip's rows already lose to the dense kernel by 2.1-52x,
+    while the paged kernels run the dense kernels' instruction stream plus
+    one scalar table load per wave and tile.  Measured
+    (scripts/bench_decode_paged.py --gather, profiles/r12_decode_paged.md):
+    B = 16, D = 128, H/Hkv 32/8 and 32/1, kv_len 2048 and 8192: the kernel
+    ahead on all four rows with disjoint ranges, 28-67x.  Every other shape
+    passes on the argument above: extrapolated, not timed."""
+    return True
+
+
+def _decode_paged_gather(k_pool, v_pool, block_table, kv_len):
+    """The needed pages as dense caches [B, Hkv, MP * PS, D], the clamped
+    lengths [B] and the keys [B, MP * PS] that sit in a page the table names
+    inside [0, P).  Unneeded and out-of-range entries are replaced by page 0
+    before they index the pool."""
+    P, Hkv, PS, D = k_pool.shape
+    B, MP = block_table.shape
+    dev = k_pool.device
+    if isinstance(kv_len, torch.Tensor):
+        n = kv_len.to(dev).long().clamp(0, MP * PS)
+    else:
+        n = torch.full((B,), min(max(int(kv_len), 0), MP * PS),
+                       dtype=torch.long, device=dev)
+    tbl = block_table.to(dev).long()
+    needed = torch.arange(MP, device=dev).view(1, MP) * PS < n.view(B, 1)
+    good = needed & (tbl >= 0) & (tbl < P)
+    idx = torch.where(good, tbl, torch.zeros_like(tbl))
+    kd = k_pool[idx].permute(0, 2, 1, 3, 4).reshape(B, Hkv, MP * PS, D)
+    vd = v_pool[idx].permute(0, 2, 1, 3, 4).reshape(B, Hkv, MP * PS, D)
+    return kd, vd, n, good.repeat_interleave(PS, dim=1)
+
+
+def _decode_paged(q, k_pool, v_pool, block_table, kv_len, scale, num_splits,
+                  impl, k_scale, v_scale):
+    """flash_attn_decode with a block_table (its docstring has the
+    contract)."""
+    if k_scale is not None or v_scale is not None \
+            or k_pool.dtype in (_FP8, torch.uint8):
+        raise RuntimeError("flash_attn_decode: block_table with an fp8 cache "
+                           "(k_scale / v_scale): fp8 pools are not supported")
+    _decode_check_shapes(q, k_pool, v_pool, block_table)
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    B, MP = block_table.shape
+    L = MP * k_pool.shape[2]
+    if not flash_attn_decode_on_hip(q, k_pool, v_pool, kv_len, impl,
+                                    block_table=block_table):
+        if k_pool.shape[0] == 0 or MP == 0:    # no page to gather
+            return (q.new_zeros(q.shape),
+                    torch.full(q.shape[:2], float("-inf"),
+                               dtype=torch.float32, device=q.device))
+        kd, vd, n, keep = _decode_paged_gather(k_pool, v_pool, block_table,
+                                               kv_len)
+        return _decode_torch(q, kd, vd, n, scale, keep_keys=keep)
+    why = _decode_paged_ineligible(q, k_pool, v_pool, block_table, kv_len)
+    if why is not None:
+        raise RuntimeError(f"flash_attn_decode(impl={impl!r}): {why}")
+    if impl is None:
+        impl = _decode_env()
+        if impl == "auto":
+            impl = "mfma" if _decode_auto_mfma(
+                q.shape[1] // k_pool.shape[1], q.shape[2], B,
+                k_pool.shape[1], L) else "hip"
+    if not isinstance(kv_len, torch.Tensor):
+        kv_len = torch.full((B,), min(max(int(kv_len), 0), L),
+                            dtype=torch.int32, device=q.device)
+    kernel = ext().flash_attn_decode_paged_mfma if impl == "mfma" \
+        else ext().flash_attn_decode_paged
+    out, lse = kernel(q, k_pool, v_pool, block_table, kv_len, float(scale),
+                      int(num_splits))
+    return out, lse
 
 
 def _decode_is_fp8(k_cache, v_cache, k_scale, v_scale) -> bool:
@@ -742,7 +861,8 @@ def _decode_fp8_ineligible(q, k_cache, v_cache, k_scale, v_scale,
 
 
 def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None,
-                             k_scale=None, v_scale=None) -> bool:
+                             k_scale=None, v_scale=None,
+                             block_table=None) -> bool:
     """Whether flash_attn_decode sends this call to a HIP kernel (with
     impl="hip" always: an ineligible input is then an error there).  The
     generators ask before they choose between the device length tensor and
@@ -751,6 +871,13 @@ def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None,
         return False
     if impl in ("hip", "mfma"):
         return True
+    if block_table is not None:
+        return (_decode_paged_ineligible(q, k_cache, v_cache, block_table,
+                                         kv_len) is None
+                and "fa" not in _TORCH_FB
+                and _decode_auto_paged_hip(
+                    q.shape[0], k_cache.shape[1],
+                    block_table.shape[1] * k_cache.shape[2]))
     if k_scale is not None or k_cache.dtype in (_FP8, torch.uint8):
         # the one HIP kernel for the dtype; no row of
         # profiles/r10_decode_fp8.md has the torch branch ahead of it
@@ -766,7 +893,7 @@ def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None,
 
 def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
                       num_splits: int = 0, impl=None, k_scale=None,
-                      v_scale=None):
+                      v_scale=None, block_table=None):
     """Attention of ONE new token per sequence over a KV cache.
 
     q [B, H, D]; k_cache, v_cache [B, Hkv, L, D] (H % Hkv == 0), taken with
@@ -793,10 +920,24 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
     HIP kernel (ops/hip/attention_decode_fp8.hip), which None, "hip" and
     "mfma" all reach.  num_splits (HIP only): 0 lets the launcher choose
     from B, Hkv, L and the CU count (never from the values of kv_len, so a
-    captured graph stays valid); >= 1 forces it."""
+    captured graph stays valid); >= 1 forces it.
+
+    Paged cache: with block_table (int32 [B, MP] on q's device) k_cache and
+    v_cache are page pools [P, Hkv, PS, D], PS in {32, 64, 128, 256}, taken
+    with their strides (a layer slice of [n_layer, P, Hkv, PS, D] is read in
+    place).  Key j of row b is row j % PS of page block_table[b, j // PS] and
+    kv_len is clamped to [0, MP * PS].  Entries past ceil(kv_len[b] / PS) may
+    hold anything; a needed entry outside [0, P) is a page of masked keys.
+    impl keeps its meaning ("hip" / "mfma" are the paged variants of the two
+    kernels, bit-identical to the dense ones on the same values; "torch"
+    gathers the needed pages into a dense cache); the split count comes from
+    B, Hkv, MP * PS and the CU count.  fp8 pools are not supported."""
     if impl not in _DECODE_IMPLS:
         raise ValueError("flash_attn_decode: impl must be None, 'torch', "
                          f"'hip' or 'mfma', got {impl!r}")
+    if block_table is not None:
+        return _decode_paged(q, k_cache, v_cache, block_table, kv_len, scale,
+                             num_splits, impl, k_scale, v_scale)
     _decode_check_shapes(q, k_cache, v_cache)
     fp8 = _decode_is_fp8(k_cache, v_cache, k_scale, v_scale)
     if scale is None:
@@ -905,6 +1046,68 @@ def kv_cache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale,
                                     v_scale, end)
     ext().kv_cache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale,
                               v_scale, end)
+
+
+def _kv_append_paged_torch(k_new, v_new, k_pool, v_pool, block_table, end):
+    """kv_cache_append_paged in torch ops, the same definition."""
+    B, S, Hkv, D = k_new.shape
+    P, PS = k_pool.shape[0], k_pool.shape[2]
+    MP = block_table.shape[1]
+    if MP == 0 or P == 0:
+        return
+    dev = k_new.device
+    tgt = end.to(dev).long().view(B, 1) - S + torch.arange(S, device=dev)
+    slot = torch.div(tgt, PS, rounding_mode="floor").clamp(0, MP - 1)
+    page = block_table.to(dev).long().gather(1, slot)          # [B, S]
+    ok = (tgt >= 0) & (tgt < MP * PS) & (page >= 0) & (page < P)
+    bi, si = torch.nonzero(ok, as_tuple=True)
+    pi, ri = page[bi, si], (tgt % PS)[bi, si]
+    for x, pool in ((k_new, k_pool), (v_new, v_pool)):
+        pool[pi, :, ri] = x[bi, si]                            # [n, Hkv, D]
+
+
+def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
+                          impl=None):
+    """Copy new K / V rows into a paged KV cache, in place.
+
+    k_new, v_new [B, S, Hkv, D], taken with their strides (views into a
+    fused qkv output are read in place); k_pool, v_pool [P, Hkv, PS, D] of
+    the same dtype, with their strides too (a layer slice is written in
+    place); block_table int32 [B, MP]; end int32 [B]: the length AFTER the
+    append, so row s of batch b goes to logical position j = end[b] - S + s:
+    row j % PS of page block_table[b, j // PS].  Rows with j outside
+    [0, MP * PS) and rows whose page id is outside [0, P) are dropped;
+    nothing else in the pools changes.
+
+    impl: "hip" = ops/hip/kv_cache_paged.hip (2-byte dtypes, PS in {32, 64,
+    128, 256}), one launch for K and V with position and page read on the
+    device (no host sync: capturable); "torch" = the same definition in
+    torch ops; None = the kernel on the GPU for 2-byte dtypes, else torch
+    (and with HETU_AMD_TORCH_FALLBACK=fa)."""
+    if impl not in (None, "torch", "hip"):
+        raise ValueError("kv_cache_append_paged: impl must be None, 'torch' "
+                         f"or 'hip', got {impl!r}")
+    if k_new.dim() != 4 or k_new.shape != v_new.shape or k_pool.dim() != 4 \
+            or k_pool.shape != v_pool.shape \
+            or k_pool.shape[1] != k_new.shape[2] \
+            or k_pool.shape[3] != k_new.shape[3] \
+            or block_table.dim() != 2 \
+            or block_table.shape[0] != k_new.shape[0] \
+            or tuple(end.shape) != (k_new.shape[0],):
+        raise ValueError(
+            "kv_cache_append_paged: need k_new, v_new [B, S, Hkv, D], pools "
+            "[P, Hkv, PS, D], block_table [B, MP] and end [B]; got "
+            f"{tuple(k_new.shape)}, {tuple(v_new.shape)}, "
+            f"{tuple(k_pool.shape)}, {tuple(v_pool.shape)}, "
+            f"{tuple(block_table.shape)}, {tuple(end.shape)}")
+    if impl is None:
+        impl = "hip" if (k_new.is_cuda and k_new.element_size() == 2
+                         and "fa" not in _TORCH_FB) else "torch"
+    if impl == "torch":
+        return _kv_append_paged_torch(k_new, v_new, k_pool, v_pool,
+                                      block_table, end)
+    ext().kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table,
+                                end)
 
 
 # ---------------------------------------------------------------------------

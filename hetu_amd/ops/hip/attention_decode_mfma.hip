@@ -42,9 +42,23 @@
 // staged image holds valid rows only (0 x NaN is NaN inside an MFMA); the
 // score of a key past the end is selected to -inf and its p to 0; a wave
 // whose 32 keys are all past the end skips the tile.
+//
+// PAGED (flash_attn_decode_paged_mfma): k / v are page pools [P, Hkv, PS, D]
+// behind a block table (attention_decode.h).  A wave's 32 keys of a tile are
+// aligned to 32 and PS >= 32, so they share one page: its id is a scalar that
+// offsets the K row pointer and the per-lane source address of the V DMA;
+// rows are clamped as above and then reduced mod PS.  The LDS image, swizzle,
+// ring and waits are the dense kernel's.  Ids run two tiles ahead of the
+// MFMAs: the trip of tile i issues V(i + 1) and reloads K(i + 1) with the id
+// it already holds and requests the id of tile i + 2, so no K / V address
+// waits for the table.  A page id outside [0, P) is 32 masked keys: the tile
+// is neither loaded nor scored (the loop head then drains instead of counting
+// a DMA that was not issued).  Same tiles, streams and merge order as the
+// dense kernel: bit-identical results for the same values.
 #include <ATen/hip/HIPContext.h>
 #include "ext_stream.h"
 #include "attention_common.h"
+#include <type_traits>
 #include "attention_decode.h"
 
 namespace {
@@ -64,17 +78,19 @@ DEV int dm_swz(int row) {
   return D == 128 ? (row & 7) : ((row >> 1) & 3);
 }
 
-// stage keys k0 .. k0 + 31 (clamped to klast) of V into a wave's image
+// stage keys k0 .. k0 + 31 (clamped to klast) of V into a wave's image; a
+// row index is taken & rmask (-1: dense; PS - 1: the row within vb's page)
 template <int D>
 DEV void dm_stage_v(const bf16* vb, long long v_rs, int k0, int klast,
-                    char* img, int lane) {
+                    int rmask, char* img, int lane) {
   constexpr int RB = 2 * D;
 #pragma unroll
   for (int i = 0; i < DM_WKEYS * RB / 1024; ++i) {
     const int pos = (i * WAVE + lane) * 16;
     const int row = pos / RB;
     const int col = ((pos % RB) ^ (dm_swz<D>(row) << 5)) >> 1;
-    fa_glds16(vb + (int64_t)min(k0 + row, klast) * v_rs + col, img + pos);
+    fa_glds16(vb + (int64_t)(min(k0 + row, klast) & rmask) * v_rs + col,
+              img + pos);
   }
 }
 
@@ -82,11 +98,11 @@ DEV void dm_stage_v(const bf16* vb, long long v_rs, int k0, int klast,
 // 32 ks + 8 g .. + 8
 template <int D>
 DEV void dm_load_k(bf16x8 (&kf)[2][D / 32], const bf16* kb, long long k_rs,
-                   int k0, int klast, int lane) {
+                   int k0, int klast, int rmask, int lane) {
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const bf16* row = kb + (int64_t)min(k0 + 16 * c + (lane & 15), klast) *
-                               k_rs + 8 * (lane >> 4);
+    const bf16* row = kb + (int64_t)(min(k0 + 16 * c + (lane & 15), klast) &
+                                     rmask) * k_rs + 8 * (lane >> 4);
 #pragma unroll
     for (int ks = 0; ks < D / 32; ++ks)
       kf[c][ks] = *reinterpret_cast<const bf16x8*>(row + 32 * ks);
@@ -127,9 +143,9 @@ DEV void dm_tr_v4(bf16x8 (&vt)[4], const char* img, int db0, int lane) {
 
 // two blocks per CU (2 waves / SIMD, 256 registers a lane) wherever that
 // compiles without scratch: all but D = 128 with two or four head tiles
-template <int D, int MT>
+template <int D, int MT, bool PAGED = false>
 __global__ __launch_bounds__(DM_THREADS, (D == 128 && MT >= 2) ? 1 : 2)
-void fa_decode_mfma_kernel(DecArgs a) {
+void fa_decode_mfma_kernel(std::conditional_t<PAGED, DecPagedArgs, DecArgs> a) {
   constexpr int RB = 2 * D;
   constexpr int IMG = DM_WKEYS * RB;           // 8 KiB (D = 128) / 4 KiB
   constexpr int NV = IMG / 1024;               // DMA instructions per tile
@@ -172,8 +188,21 @@ void fa_decode_mfma_kernel(DecArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hi = lane & 15;            // head column / key row of a fragment
   const int lg = lane >> 4;            // lane group
-  const bf16* kb = a.k + (int64_t)b * a.k_bs + (int64_t)hkv * a.k_hs;
-  const bf16* vb = a.v + (int64_t)b * a.v_bs + (int64_t)hkv * a.v_hs;
+  // dense: the batch row's cache; paged: the pool, kpage / vpage add the page
+  const bf16* kb = a.k + (PAGED ? 0 : (int64_t)b * a.k_bs) +
+                   (int64_t)hkv * a.k_hs;
+  const bf16* vb = a.v + (PAGED ? 0 : (int64_t)b * a.v_bs) +
+                   (int64_t)hkv * a.v_hs;
+  const auto kpage = [&](int page) {
+    if constexpr (PAGED) return kb + (int64_t)page * a.k_bs;
+    else return kb;
+  };
+  const auto vpage = [&](int page) {
+    if constexpr (PAGED) return vb + (int64_t)page * a.v_bs;
+    else return vb;
+  };
+  int rmask = -1;                      // row within the page
+  if constexpr (PAGED) rmask = (1 << a.ps_shift) - 1;
   const float scale = a.scale;
   // this split's keys; every address is clamped to klast < kv <= L
   const int kend = min(t1 * DEC_BN, kv), klast = kend - 1;
@@ -210,18 +239,49 @@ void fa_decode_mfma_kernel(DecArgs a) {
     }
 
     bf16x8 kf[2][KS];
-    if (nt > 0) {
-      dm_load_k<D>(kf, kb, a.k_rs, kw0, klast, lane);
-      dm_stage_v<D>(vb, a.v_rs, kw0, klast, ring, lane);
+    // paged: the page id of tile i + 1 and whether tile i has a page at all
+    // (dense: no ids, every tile has)
+    [[maybe_unused]] int page_nx = 0;
+    bool ok = true;
+    if constexpr (PAGED) {
+      const int page = dec_page_of(a, b, min(kw0, klast));
+      page_nx = dec_page_of(a, b, min(kw0 + DM_BN, klast));
+      ok = (unsigned)page < (unsigned)a.P;
+      if (nt > 0 && ok) {
+        dm_load_k<D>(kf, kpage(page), a.k_rs, kw0, klast, rmask, lane);
+        dm_stage_v<D>(vpage(page), a.v_rs, kw0, klast, rmask, ring, lane);
+      }
+    } else if (nt > 0) {
+      dm_load_k<D>(kf, kb, a.k_rs, kw0, klast, rmask, lane);
+      dm_stage_v<D>(vb, a.v_rs, kw0, klast, rmask, ring, lane);
     }
     for (int i = 0; i < nt; ++i) {     // wave-uniform trip count
       const int k0 = kw0 + i * DM_BN;
       const bool last = i + 1 == nt;
       const char* img = ring + (i & 1) * IMG;
-      if (!last)
-        dm_stage_v<D>(vb, a.v_rs, k0 + DM_BN, klast,
+      bool more = !last;               // tile i + 1 is loaded in this trip
+      [[maybe_unused]] int page_nn = 0;
+      if constexpr (PAGED) {
+        // tile i + 2's id: first used one trip from here
+        int key_nn = min(k0 + 2 * DM_BN, klast);
+        dec_page_landed(page_nx, key_nn);
+        page_nn = dec_page_of(a, b, key_nn);
+        more = !last && (unsigned)page_nx < (unsigned)a.P;
+      }
+      if (more)
+        dm_stage_v<D>(vpage(page_nx), a.v_rs, k0 + DM_BN, klast, rmask,
                       ring + ((i + 1) & 1) * IMG, lane);
-      fa_wait_tile<NV>(last);          // K(i) and V(i) are in
+      if constexpr (PAGED) {
+        if (!ok) {                     // 32 masked keys: nothing was loaded
+          if (more)
+            dm_load_k<D>(kf, kpage(page_nx), a.k_rs, k0 + DM_BN, klast, rmask,
+                         lane);
+          page_nx = page_nn;
+          ok = more;
+          continue;
+        }
+      }
+      fa_wait_tile<NV>(!more);         // K(i) and V(i) are in
       __builtin_amdgcn_sched_barrier(0);   // no MFMA above the DMA issue
 
       f32x4 s[MT][2];
@@ -235,7 +295,9 @@ void fa_decode_mfma_kernel(DecArgs a) {
             s[mt][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 kf[c][ks], qf[mt][ks], s[mt][c], 0, 0, 0);
         }
-      if (!last) dm_load_k<D>(kf, kb, a.k_rs, k0 + DM_BN, klast, lane);
+      if (more)
+        dm_load_k<D>(kf, kpage(page_nx), a.k_rs, k0 + DM_BN, klast, rmask,
+                     lane);
 
       // lane (lg, hi) holds keys k0 + 16 c + 4 lg + r of head hi; the tile's
       // first key is valid, so every head's new maximum is finite
@@ -285,6 +347,10 @@ void fa_decode_mfma_kernel(DecArgs a) {
             acc[mt][4 * q4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 vt[j], pf[mt], acc[mt][4 * q4 + j], 0, 0, 0);
       }
+      if constexpr (PAGED) {
+        page_nx = page_nn;
+        ok = more;
+      }
     }
 
     // the wave's stream: l over the lane groups (m is already common)
@@ -295,7 +361,8 @@ void fa_decode_mfma_kernel(DecArgs a) {
     }
     // merge the waves in wave order, one head tile at a time, through the
     // bytes of the rings; thread = (head of the tile, DPT dims).  The split
-    // is not empty, so wave 0 met a valid key: mx is finite.
+    // is not empty, so wave 0 met a valid key: mx is finite (paged: unless
+    // every page of the split is out of range; `none`).
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       __syncthreads();                 // rings / the previous tile are done
@@ -315,22 +382,23 @@ void fa_decode_mfma_kernel(DecArgs a) {
         float mx = s_m[hh];
 #pragma unroll
         for (int w = 1; w < DM_WAVES; ++w) mx = fmaxf(mx, s_m[w * 16 + hh]);
+        const bool none = PAGED && mx == -INFINITY;
         float lt = 0.f, o[DPT];
 #pragma unroll
         for (int j = 0; j < DPT; ++j) o[j] = 0.f;
 #pragma unroll
         for (int w = 0; w < DM_WAVES; ++w) {
-          const float ww = __expf(s_m[w * 16 + hh] - mx);
+          const float ww = none ? 0.f : __expf(s_m[w * 16 + hh] - mx);
           lt += s_l[w * 16 + hh] * ww;
 #pragma unroll
           for (int j = 0; j < DPT; ++j)
             o[j] += s_o[(w * 16 + hh) * DP + d0 + j] * ww;
         }
-        const float inv = 1.f / lt;
+        const float inv = none ? 0.f : 1.f / lt;
 #pragma unroll
         for (int j = 0; j < DPT; ++j) o[j] *= inv;
         const int64_t row = row0 + head;
-        const float ls = mx + logf(lt);
+        const float ls = none ? -INFINITY : mx + logf(lt);
         if (ns == 1) {
           bf16* dst = a.out + row * D + d0;
 #pragma unroll
@@ -369,6 +437,37 @@ std::vector<torch::Tensor> flash_attn_decode_mfma(torch::Tensor q,
   const dim3 grid(a.ns, (unsigned)c.Hkv, (unsigned)c.B);
 #define DM_LAUNCH(DD, MM)                                                  \
   hipLaunchKernelGGL((fa_decode_mfma_kernel<DD, MM>), grid,                \
+                     dim3(DM_THREADS), 0, stream, a)
+#define DM_LAUNCH_D(DD)                                                    \
+  do {                                                                     \
+    if (mt == 1) DM_LAUNCH(DD, 1);                                         \
+    else if (mt == 2) DM_LAUNCH(DD, 2);                                    \
+    else DM_LAUNCH(DD, DM_MAX_MT);                                         \
+  } while (0)
+  if (c.D == 128) DM_LAUNCH_D(128);
+  else DM_LAUNCH_D(64);
+#undef DM_LAUNCH_D
+#undef DM_LAUNCH
+  HIP_CHECK(hipGetLastError());
+  if (a.ns > 1) dec_merge_launch(c, stream);
+  return {c.out, c.lse};
+}
+
+std::vector<torch::Tensor> flash_attn_decode_paged_mfma(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor block_table, torch::Tensor kv_len, double scale,
+    int64_t num_splits) {
+  // the id prefetch forms keys up to two tiles past the last one
+  DecCall c = dec_prepare(q, k_pool, v_pool, kv_len, scale, num_splits,
+                          3 * DM_BN, &block_table);
+  if (c.empty) return {c.out, c.lse};
+  const DecPagedArgs a = c.paged();
+  const int64_t G = c.H / c.Hkv;
+  const int mt = G <= 16 ? 1 : G <= 32 ? 2 : DM_MAX_MT;
+  auto stream = hetu_current_stream();
+  const dim3 grid(a.ns, (unsigned)c.Hkv, (unsigned)c.B);
+#define DM_LAUNCH(DD, MM)                                                  \
+  hipLaunchKernelGGL((fa_decode_mfma_kernel<DD, MM, true>), grid,          \
                      dim3(DM_THREADS), 0, stream, a)
 #define DM_LAUNCH_D(DD)                                                    \
   do {                                                                     \

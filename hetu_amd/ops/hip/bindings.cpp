@@ -166,6 +166,19 @@ std::vector<torch::Tensor> flash_attn_decode_mfma(torch::Tensor q,
                                                   torch::Tensor kv_len,
                                                   double scale,
                                                   int64_t num_splits);
+std::vector<torch::Tensor> flash_attn_decode_paged_mfma(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor block_table, torch::Tensor kv_len, double scale,
+    int64_t num_splits);
+// attention_decode_paged.hip
+std::vector<torch::Tensor> flash_attn_decode_paged(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor block_table, torch::Tensor kv_len, double scale,
+    int64_t num_splits);
+// kv_cache_paged.hip
+void kv_cache_append_paged(torch::Tensor k_new, torch::Tensor v_new,
+                           torch::Tensor k_pool, torch::Tensor v_pool,
+                           torch::Tensor block_table, torch::Tensor end);
 // attention_decode_fp8.hip
 int64_t decode_attn_fp8_tile();
 std::vector<torch::Tensor> flash_attn_decode_fp8(
@@ -262,4 +275,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"),
         py::arg("num_splits") = 0);
   m.def("kv_cache_append_fp8", &kv_cache_append_fp8);
+  m.def("flash_attn_decode_paged", &flash_attn_decode_paged, py::arg("q"),
+        py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+        py::arg("kv_len"), py::arg("scale"), py::arg("num_splits") = 0);
+  m.def("flash_attn_decode_paged_mfma", &flash_attn_decode_paged_mfma,
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("kv_len"), py::arg("scale"),
+        py::arg("num_splits") = 0);
+  m.def("kv_cache_append_paged", &kv_cache_append_paged);
 }

@@ -36,7 +36,9 @@ SOURCES = [
     "attention_decode.hip",
     "attention_decode_mfma.hip",
     "attention_decode_fp8.hip",
+    "attention_decode_paged.hip",
     "kv_cache_fp8.hip",
+    "kv_cache_paged.hip",
     "quant.hip",
     "moe.hip",
     "ltgemm.cpp",
@@ -54,6 +56,12 @@ EXTRA_FLAGS = {
     "attention_decode_mfma.hip": _NO_PK_F32,
     "attention_decode_fp8.hip": _NO_PK_F32,
     "kv_cache_fp8.hip": _NO_PK_F32,
+    "kv_cache_paged.hip": _NO_PK_F32,
+    # attention_decode_paged.hip instantiates attention_decode.hip's kernel
+    # (attention_decode_valu.h) and has to stay bit-identical to it, so it
+    # takes that file's flags: which multiplies and adds become fmas follows
+    # from how they are paired into packed ops, and a different choice moves
+    # lse by an ulp
     "gemm_grouped.hip": _NO_PK_F32,
 }
 
