@@ -13,6 +13,12 @@ the CPU, and for other dtypes or head dims, it is fp32 torch math on the
 visible slice of the cache.  All norms / RoPE / SwiGLU hit the same HIP
 kernels as training via ops.functional.
 
+With kv_layout="paged" the cache is a page pool behind a block table and
+generate() takes ragged prompts.  prefill="sequence" prefills them one at a
+time through the dense path; prefill="packed" runs them as one packed forward
+over the pages (F.flash_attn_prefill_paged), optionally in rounds of
+prefill_chunk tokens that attend the context already cached.
+
 Weights load from a hetu_amd checkpoint dir (utils/checkpoint format,
 incl. checkpoints converted from HF with utils/hf_convert) or from an
 in-memory state dict.
@@ -116,6 +122,17 @@ class PagedKVCache:
         self.k = torch.zeros(shape, device=device, dtype=dtype)
         self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.kv_len = torch.zeros(len(need), device=device, dtype=torch.int32)
+        self.cu_q = None               # set by packed(): a packed forward
+
+    def packed(self, cu_q, max_q: int, pos) -> "PagedKVCache":
+        """The same cache for one packed forward of ragged chunks: cu_q int32
+        [B + 1] bounds the chunks in the packed rows, max_q is the longest,
+        pos [T] each row's position; kv_len already holds the lengths after
+        the chunks."""
+        one = object.__new__(PagedKVCache)
+        one.__dict__.update(self.__dict__)
+        one.cu_q, one.max_q, one.pos = cu_q, max_q, pos
+        return one
 
     def row(self, b: int) -> "PagedKVCache":
         """Sequence b alone (B = 1) on the same pools, for its prefill."""
@@ -132,10 +149,26 @@ class LlamaGenerator:
                  dtype: torch.dtype = torch.float32,
                  decode_impl: Optional[str] = None,
                  kv_dtype: Optional[str] = None,
-                 kv_layout: str = "dense", page_size: int = 64):
+                 kv_layout: str = "dense", page_size: int = 64,
+                 prefill: str = "sequence",
+                 prefill_chunk: Optional[int] = None):
         if kv_layout not in ("dense", "paged"):
             raise ValueError(f"kv_layout must be 'dense' or 'paged', got "
                              f"{kv_layout!r}")
+        if prefill not in ("sequence", "packed"):
+            raise ValueError(f"prefill must be 'sequence' or 'packed', got "
+                             f"{prefill!r}")
+        if prefill != "sequence" and kv_layout != "paged":
+            raise ValueError("prefill='packed' needs kv_layout='paged'")
+        if prefill_chunk is not None and (prefill != "packed"
+                                          or prefill_chunk < 1):
+            raise ValueError("prefill_chunk needs prefill='packed' and a "
+                             f"positive size, got {prefill_chunk!r}")
+        # "packed": all prompts in one forward over the paged cache
+        # (F.flash_attn_prefill_paged), in rounds of at most prefill_chunk
+        # tokens per sequence
+        self.prefill = prefill
+        self.prefill_chunk = prefill_chunk
         if kv_layout == "paged" and kv_dtype is not None:
             raise ValueError("kv_layout='paged' holds the model dtype; "
                              "kv_dtype='fp8' is dense only")
@@ -183,8 +216,10 @@ class LlamaGenerator:
     def _attn_paged(self, x, layer, cache: PagedKVCache):
         """S > 1: the prefill of one sequence (cache = its row(), still
         empty) on the rows it just computed; S == 1: a decode step of all
-        sequences.  cache.kv_len is the length after the append in both, and
-        positions, append and attention read it on the device."""
+        sequences; a cache from packed(): ragged chunks of all sequences in
+        one row of x, over the pages.  cache.kv_len is the length after the
+        append in all three, and append and attention read it on the
+        device."""
         cfg = self.cfg
         B, S, _ = x.shape
         H, Hkv = cfg.n_head, cfg.n_kv_head
@@ -196,6 +231,20 @@ class LlamaGenerator:
         v = v.view(B, S, Hkv, dh)
         kp, vp = cache.k[layer], cache.v[layer]
         wo = self.w[f"l{layer}.attn.wo.weight"]
+        if cache.cu_q is not None:
+            # packed chunks (B == 1, S = all rows): one RoPE row per token
+            # from its own position, then append and attention over the
+            # pages, the cached context included
+            cos, sin = self.cos[cache.pos], self.sin[cache.pos]
+            q = F.rope_fwd(q[0], cos, sin)
+            k = F.rope_fwd(k[0], cos, sin)
+            F.kv_cache_append_paged(k, v[0], kp, vp, cache.block_table,
+                                    cache.kv_len, cu_q=cache.cu_q,
+                                    max_q=cache.max_q)
+            o, _ = F.flash_attn_prefill_paged(
+                q, kp, vp, cache.block_table, cache.cu_q, cache.kv_len,
+                self.scale, max_q=cache.max_q)
+            return o.reshape(1, S, H * dh) @ wo.t()
         if S == 1:
             # one RoPE row per sequence, gathered from its own position; the
             # batch takes the place of the packed form's sequence dim
@@ -311,12 +360,41 @@ class LlamaGenerator:
         x = x + h @ self.w[f"l{layer}.mlp.w_out.weight"].t()
         return x
 
-    def _forward(self, ids, cache, pos0):
+    def _hidden(self, ids, cache, pos0):
         x = self.w["wte.weight"][ids]
         for layer in range(self.cfg.n_layer):
             x = self._block(x, layer, cache, pos0)
-        x = F.rmsnorm_fwd(x, self.w["lnf.weight"], self.cfg.rms_eps)[0]
+        return F.rmsnorm_fwd(x, self.w["lnf.weight"], self.cfg.rms_eps)[0]
+
+    def _forward(self, ids, cache, pos0):
+        x = self._hidden(ids, cache, pos0)
         return x[:, -1] @ self.w["lm_head.weight"].t()   # last-token logits
+
+    def _prefill_packed(self, prompts, lens, cache: PagedKVCache):
+        """All prompts through packed forwards over the paged cache, in
+        rounds of at most prefill_chunk tokens per sequence (one round
+        without it) -> last-token logits [B, vocab].  A finished sequence
+        contributes zero rows to later rounds."""
+        B = len(prompts)
+        step = self.prefill_chunk or max(lens, default=0)
+        logits = [None] * B
+        for done in range(0, max(lens, default=0), max(step, 1)):
+            lo = [min(done, n) for n in lens]
+            hi = [min(done + step, n) for n in lens]
+            cu = [0]
+            for a, e in zip(lo, hi):
+                cu.append(cu[-1] + e - a)
+            cache.kv_len.copy_(torch.tensor(hi, dtype=torch.int32))
+            ids = torch.cat([p[a:e] for p, a, e in zip(prompts, lo, hi)])
+            pos = torch.cat([torch.arange(a, e) for a, e in zip(lo, hi)])
+            view = cache.packed(
+                torch.tensor(cu, dtype=torch.int32).to(self.device),
+                max(e - a for a, e in zip(lo, hi)), pos.to(self.device))
+            x = self._hidden(ids.unsqueeze(0), view, None)[0]
+            for b in range(B):
+                if lo[b] < hi[b] == lens[b]:       # held its last token
+                    logits[b] = x[cu[b + 1] - 1]
+        return torch.stack(logits) @ self.w["lm_head.weight"].t()
 
     # ---- public API ------------------------------------------------------
     @torch.no_grad()
@@ -364,9 +442,12 @@ class LlamaGenerator:
                              self.page_size, self.device, self.dtype)
         gen = torch.Generator(device="cpu").manual_seed(seed)
         cache.kv_len.copy_(torch.tensor(lens, dtype=torch.int32))
-        # prefill: one sequence at a time through the dense prefill path
-        logits = torch.cat([self._forward(p.unsqueeze(0), cache.row(b), 0)
-                            for b, p in enumerate(prompts)])
+        if self.prefill == "packed":
+            logits = self._prefill_packed(prompts, lens, cache)
+        else:
+            # one sequence at a time through the dense prefill path
+            logits = torch.cat([self._forward(p.unsqueeze(0), cache.row(b), 0)
+                                for b, p in enumerate(prompts)])
         new = []
         alive = torch.ones(B, dtype=torch.bool)
         for _ in range(max_new_tokens):

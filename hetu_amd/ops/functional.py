@@ -1066,8 +1066,30 @@ def _kv_append_paged_torch(k_new, v_new, k_pool, v_pool, block_table, end):
         pool[pi, :, ri] = x[bi, si]                            # [n, Hkv, D]
 
 
+def _kv_append_paged_packed_torch(k_new, v_new, k_pool, v_pool, block_table,
+                                  end, cu_q):
+    """kv_cache_append_paged with cu_q in torch ops, the same definition."""
+    T = k_new.shape[0]
+    P, PS = k_pool.shape[0], k_pool.shape[2]
+    B, MP = block_table.shape
+    if MP == 0 or P == 0:
+        return
+    dev = k_new.device
+    cu = [min(max(int(c), 0), T) for c in cu_q.tolist()]
+    tbl = block_table.to(dev).long()
+    for b, e in enumerate(end.tolist()):
+        lo, hi = cu[b], max(cu[b + 1], cu[b])
+        n = hi - lo
+        tgt = int(e) - n + torch.arange(n, device=dev)
+        slot = torch.div(tgt, PS, rounding_mode="floor").clamp(0, MP - 1)
+        page = tbl[b][slot]
+        ok = (tgt >= 0) & (tgt < MP * PS) & (page >= 0) & (page < P)
+        for x, pool in ((k_new, k_pool), (v_new, v_pool)):
+            pool[page[ok], :, (tgt % PS)[ok]] = x[lo:hi][ok]
+
+
 def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
-                          impl=None):
+                          cu_q=None, max_q=None, impl=None):
     """Copy new K / V rows into a paged KV cache, in place.
 
     k_new, v_new [B, S, Hkv, D], taken with their strides (views into a
@@ -1079,6 +1101,13 @@ def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
     [0, MP * PS) and rows whose page id is outside [0, P) are dropped;
     nothing else in the pools changes.
 
+    Packed rows: with cu_q (int32 [B + 1]) k_new, v_new are [T, Hkv, D],
+    packed over sequences; sequence b holds the n_b = cu_q[b + 1] - cu_q[b]
+    rows from cu_q[b] and row t of it goes to position
+    end[b] - n_b + (t - cu_q[b]), with the same drop rules.  max_q, an upper
+    bound on the longest chunk (default T), only sizes the grid: rows of a
+    longer chunk past it are not copied.
+
     impl: "hip" = ops/hip/kv_cache_paged.hip (2-byte dtypes, PS in {32, 64,
     128, 256}), one launch for K and V with position and page read on the
     device (no host sync: capturable); "torch" = the same definition in
@@ -1087,6 +1116,31 @@ def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
     if impl not in (None, "torch", "hip"):
         raise ValueError("kv_cache_append_paged: impl must be None, 'torch' "
                          f"or 'hip', got {impl!r}")
+    if cu_q is not None:
+        if k_new.dim() != 3 or k_new.shape != v_new.shape \
+                or k_pool.dim() != 4 or k_pool.shape != v_pool.shape \
+                or k_pool.shape[1] != k_new.shape[1] \
+                or k_pool.shape[3] != k_new.shape[2] \
+                or block_table.dim() != 2 \
+                or tuple(end.shape) != (block_table.shape[0],) \
+                or tuple(cu_q.shape) != (block_table.shape[0] + 1,):
+            raise ValueError(
+                "kv_cache_append_paged: with cu_q need k_new, v_new "
+                "[T, Hkv, D], pools [P, Hkv, PS, D], block_table [B, MP], "
+                f"end [B] and cu_q [B + 1]; got {tuple(k_new.shape)}, "
+                f"{tuple(v_new.shape)}, {tuple(k_pool.shape)}, "
+                f"{tuple(v_pool.shape)}, {tuple(block_table.shape)}, "
+                f"{tuple(end.shape)}, {tuple(cu_q.shape)}")
+        if impl is None:
+            impl = "hip" if (k_new.is_cuda and k_new.element_size() == 2
+                             and "fa" not in _TORCH_FB) else "torch"
+        if impl == "torch":
+            return _kv_append_paged_packed_torch(k_new, v_new, k_pool, v_pool,
+                                                 block_table, end, cu_q)
+        ext().kv_cache_append_paged_packed(
+            k_new, v_new, k_pool, v_pool, block_table, end, cu_q,
+            int(k_new.shape[0] if max_q is None else max_q))
+        return
     if k_new.dim() != 4 or k_new.shape != v_new.shape or k_pool.dim() != 4 \
             or k_pool.shape != v_pool.shape \
             or k_pool.shape[1] != k_new.shape[2] \
@@ -1108,6 +1162,143 @@ def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
                                       block_table, end)
     ext().kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table,
                                 end)
+
+
+def _prefill_paged_ineligible(q, k_pool, v_pool, block_table, cu_q,
+                              kv_len) -> Optional[str]:
+    """Why ops/hip/attention_prefill_paged.hip cannot take this input, or
+    None.  The reason names the argument."""
+    ts = (("q", q), ("k_pool", k_pool), ("v_pool", v_pool))
+    for name, t in ts:
+        if not t.is_cuda:
+            return f"{name} is not on the GPU"
+        if t.dtype != torch.bfloat16:
+            return f"{name} is {t.dtype}, not bf16"
+    if q.shape[-1] != 128:
+        return f"the head dim of q is {q.shape[-1]}, not 128"
+    for name, t in ts:
+        if t.stride(-1) != 1:
+            return f"{name} has a non-unit last stride"
+        if any(s % 8 for s, n in zip(t.stride()[:-1], t.shape) if n > 1) \
+                or t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned in every stride"
+    for name, t in (("block_table", block_table), ("cu_q", cu_q),
+                    ("kv_len", kv_len)):
+        if not t.is_cuda:
+            return f"{name} is not on the GPU"
+        if t.dtype != torch.int32:
+            return f"{name} is {t.dtype}, not int32"
+        if not t.is_contiguous():
+            return f"{name} is not contiguous"
+    return None
+
+
+def _prefill_paged_torch(q, k_pool, v_pool, block_table, cu_q, kv_len,
+                         scale):
+    """flash_attn_prefill_paged in fp32 torch ops: per sequence, gather its
+    keys through its table row, mask by selection, softmax."""
+    T, H, D = q.shape
+    P, Hkv, PS, _ = k_pool.shape
+    B, MP = block_table.shape
+    G = H // Hkv
+    dev = q.device
+    out = torch.zeros(T, H, D, dtype=torch.float32, device=dev)
+    lse = torch.full((H, T), float("-inf"), dtype=torch.float32, device=dev)
+    cu = [min(max(int(c), 0), T) for c in cu_q.tolist()]
+    tbl = block_table.to(dev).long()
+    for b, kv in enumerate(kv_len.tolist()):
+        lo, hi = cu[b], max(cu[b + 1], cu[b])
+        n, kv = hi - lo, min(max(int(kv), 0), MP * PS)
+        if n == 0 or kv == 0:
+            continue
+        ids = tbl[b, :-(-kv // PS)]
+        good = (ids >= 0) & (ids < P)
+        idx = torch.where(good, ids, torch.zeros_like(ids))
+        keep = good.repeat_interleave(PS)[:kv]                   # [kv]
+        if P == 0 or not bool(keep.any()):
+            continue
+
+        def keys(pool):
+            x = pool[idx].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :kv]
+            x = torch.where(keep.view(1, kv, 1), x.float(), 0.0)
+            return x.repeat_interleave(G, dim=0) if G > 1 else x
+        kf, vf = keys(k_pool), keys(v_pool)                      # [H, kv, D]
+        qf = q[lo:hi].float().permute(1, 0, 2)                   # [H, n, D]
+        pos = kv - n + torch.arange(n, device=dev)
+        vis = keep.view(1, kv) & (torch.arange(kv, device=dev).view(1, kv)
+                                  <= pos.view(n, 1))             # [n, kv]
+        s = (qf @ kf.transpose(-1, -2)) * scale
+        s = s.masked_fill(~vis, float("-inf"))
+        l = torch.logsumexp(s, dim=-1)                           # [H, n]
+        p = torch.where(vis, torch.exp(s - l.unsqueeze(-1)), 0.0)
+        out[lo:hi] = (p @ vf).permute(1, 0, 2)
+        lse[:, lo:hi] = l
+    return out.to(q.dtype), lse
+
+
+def flash_attn_prefill_paged(q, k_pool, v_pool, block_table, cu_q, kv_len,
+                             scale=None, max_q=None, impl=None):
+    """Causal attention of a packed, ragged batch of query chunks over a paged
+    KV cache, each chunk at the END of its sequence's cached keys.
+
+    q [T, H, D] packed over sequences, taken with its strides (a view into a
+    fused qkv output is read in place); k_pool, v_pool [P, Hkv, PS, D], PS in
+    {32, 64, 128, 256}, with their strides; block_table int32 [B, MP]; cu_q
+    int32 [B + 1]; kv_len int32 [B], the length AFTER the chunk was appended
+    (kv_cache_append_paged with cu_q writes it there).  With
+    n_b = cu_q[b + 1] - cu_q[b] and kv_b = clamp(kv_len[b], 0, MP * PS), row i
+    of sequence b stands at position p = kv_b - n_b + i and attends keys
+    0 .. p; key j is row j % PS of page block_table[b, j // PS].  Returns
+    (out [T, H, D] in q's dtype, lse [H, T] fp32, flash_attn_varlen_fwd's
+    layout).  A row with p < 0 attends nothing: out = 0, lse = -inf, and so do
+    rows at or past cu_q[B].  n_b == 0 is legal.  Table entries past
+    ceil(kv_b / PS) and pool rows at or past kv_b may hold anything; a needed
+    entry outside [0, P) is a page of masked keys.
+
+    max_q: an upper bound on the longest chunk, default T.  It only sizes the
+    grid (as max_seqlen does for flash_attn_varlen_bwd): rows of a longer
+    chunk past it are not computed.
+
+    impl: "hip" = ops/hip/attention_prefill_paged.hip (bf16, D = 128, GPU, any
+    H / Hkv; one launch, lengths and table read on the device, so append +
+    attention capture into one graph; an error on anything else, never a
+    fallback); "torch" = the definition in fp32 torch ops, one sequence at a
+    time (it reads cu_q and kv_len on the host); None = the kernel for every
+    eligible input, else torch (and with HETU_AMD_TORCH_FALLBACK=fa)."""
+    if impl not in (None, "torch", "hip"):
+        raise ValueError("flash_attn_prefill_paged: impl must be None, "
+                         f"'torch' or 'hip', got {impl!r}")
+    if q.dim() != 3 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape \
+            or k_pool.shape[3] != q.shape[2] or k_pool.shape[1] < 1 \
+            or q.shape[1] % k_pool.shape[1] \
+            or block_table.dim() != 2 \
+            or tuple(cu_q.shape) != (block_table.shape[0] + 1,) \
+            or tuple(kv_len.shape) != (block_table.shape[0],):
+        raise ValueError(
+            "flash_attn_prefill_paged: need q [T, H, D], k_pool, v_pool "
+            "[P, Hkv, PS, D] with H a multiple of Hkv, block_table [B, MP], "
+            f"cu_q [B + 1] and kv_len [B]; got {tuple(q.shape)}, "
+            f"{tuple(k_pool.shape)}, {tuple(v_pool.shape)}, "
+            f"{tuple(block_table.shape)}, {tuple(cu_q.shape)}, "
+            f"{tuple(kv_len.shape)}")
+    if k_pool.shape[2] not in _PAGE_SIZES:
+        raise ValueError(
+            "flash_attn_prefill_paged: the page size of k_pool / v_pool "
+            f"(dim 2) is {k_pool.shape[2]}, not one of {_PAGE_SIZES}")
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    why = _prefill_paged_ineligible(q, k_pool, v_pool, block_table, cu_q,
+                                    kv_len)
+    if impl == "hip" and why is not None:
+        raise ValueError(f"flash_attn_prefill_paged(impl='hip'): {why}")
+    if impl == "torch" or (impl is None
+                           and (why is not None or "fa" in _TORCH_FB)):
+        return _prefill_paged_torch(q, k_pool, v_pool, block_table, cu_q,
+                                    kv_len, float(scale))
+    out, lse = ext().flash_attn_prefill_paged(
+        q, k_pool, v_pool, block_table, cu_q, kv_len, float(scale),
+        int(q.shape[0] if max_q is None else max_q))
+    return out, lse
 
 
 # ---------------------------------------------------------------------------

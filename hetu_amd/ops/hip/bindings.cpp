@@ -179,6 +179,16 @@ std::vector<torch::Tensor> flash_attn_decode_paged(
 void kv_cache_append_paged(torch::Tensor k_new, torch::Tensor v_new,
                            torch::Tensor k_pool, torch::Tensor v_pool,
                            torch::Tensor block_table, torch::Tensor end);
+void kv_cache_append_paged_packed(torch::Tensor k_new, torch::Tensor v_new,
+                                  torch::Tensor k_pool, torch::Tensor v_pool,
+                                  torch::Tensor block_table,
+                                  torch::Tensor end, torch::Tensor cu_q,
+                                  int64_t max_q);
+// attention_prefill_paged.hip
+std::vector<torch::Tensor> flash_attn_prefill_paged(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor block_table, torch::Tensor cu_q, torch::Tensor kv_len,
+    double scale, int64_t max_q);
 // attention_decode_fp8.hip
 int64_t decode_attn_fp8_tile();
 std::vector<torch::Tensor> flash_attn_decode_fp8(
@@ -283,4 +293,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_table"), py::arg("kv_len"), py::arg("scale"),
         py::arg("num_splits") = 0);
   m.def("kv_cache_append_paged", &kv_cache_append_paged);
+  m.def("kv_cache_append_paged_packed", &kv_cache_append_paged_packed);
+  m.def("flash_attn_prefill_paged", &flash_attn_prefill_paged, py::arg("q"),
+        py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+        py::arg("cu_q"), py::arg("kv_len"), py::arg("scale"),
+        py::arg("max_q"));
 }
