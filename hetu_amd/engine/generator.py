@@ -17,7 +17,9 @@ With kv_layout="paged" the cache is a page pool behind a block table and
 generate() takes ragged prompts.  prefill="sequence" prefills them one at a
 time through the dense path; prefill="packed" runs them as one packed forward
 over the pages (F.flash_attn_prefill_paged), optionally in rounds of
-prefill_chunk tokens that attend the context already cached.
+prefill_chunk tokens that attend the context already cached.  kv_dtype="fp8"
+makes the pages e4m3 codes with one fp32 scale per cached row (prefill=
+"sequence" only: the prefill attends the bf16 rows it just computed).
 
 Weights load from a hetu_amd checkpoint dir (utils/checkpoint format,
 incl. checkpoints converted from HF with utils/hf_convert) or from an
@@ -97,10 +99,14 @@ class PagedKVCache:
     the sequences' own needs, not B x the longest.  Pages are handed out
     round-robin over the sequences (physical order differs from logical
     order); table entries a sequence does not own hold P, which the kernels
-    treat as a page of masked keys."""
+    treat as a page of masked keys.  kv_dtype="fp8": k, v hold e4m3 codes and
+    k_scale, v_scale [n_layer, P, Hkv, PS] one fp32 scale per cached row."""
 
     def __init__(self, cfg: LlamaConfig, capacity, page_size: int, device,
-                 dtype):
+                 dtype, kv_dtype: Optional[str] = None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got "
+                             f"{kv_dtype!r}")
         if page_size not in F._PAGE_SIZES:
             raise ValueError(f"page_size must be one of {F._PAGE_SIZES}, "
                              f"got {page_size}")
@@ -119,8 +125,18 @@ class PagedKVCache:
         self.block_table = torch.tensor(table, dtype=torch.int32) \
             .view(len(need), mp).to(device)
         shape = (cfg.n_layer, self.num_pages, cfg.n_kv_head, page_size, dh)
-        self.k = torch.zeros(shape, device=device, dtype=dtype)
-        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        self.kv_dtype = kv_dtype
+        self.k_scale = self.v_scale = None
+        if kv_dtype == "fp8":
+            self.k = torch.zeros(shape, device=device,
+                                 dtype=torch.float8_e4m3fn)
+            self.v = torch.zeros_like(self.k)
+            self.k_scale = torch.zeros(shape[:-1], device=device,
+                                       dtype=torch.float32)
+            self.v_scale = torch.zeros_like(self.k_scale)
+        else:
+            self.k = torch.zeros(shape, device=device, dtype=dtype)
+            self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.kv_len = torch.zeros(len(need), device=device, dtype=torch.int32)
         self.cu_q = None               # set by packed(): a packed forward
 
@@ -169,9 +185,10 @@ class LlamaGenerator:
         # tokens per sequence
         self.prefill = prefill
         self.prefill_chunk = prefill_chunk
-        if kv_layout == "paged" and kv_dtype is not None:
-            raise ValueError("kv_layout='paged' holds the model dtype; "
-                             "kv_dtype='fp8' is dense only")
+        if prefill == "packed" and kv_dtype == "fp8":
+            raise ValueError("prefill='packed' with kv_dtype='fp8': an fp8 "
+                             "prefill kernel over the pages does not exist "
+                             "yet; use prefill='sequence'")
         # "paged": generate() keeps the cache in a PagedKVCache of page_size
         # rows per page and also takes ragged prompts
         self.kv_layout = kv_layout
@@ -231,6 +248,14 @@ class LlamaGenerator:
         v = v.view(B, S, Hkv, dh)
         kp, vp = cache.k[layer], cache.v[layer]
         wo = self.w[f"l{layer}.attn.wo.weight"]
+        # fp8 pools: the scale pools go with the append (`app`) and the decode
+        # call (`fp8`); rows that are not bf16 take the torch append
+        fp8, app = {}, {}
+        if cache.kv_dtype == "fp8":
+            fp8 = dict(k_scale=cache.k_scale[layer],
+                       v_scale=cache.v_scale[layer])
+            app = dict(fp8, impl=None if k.dtype == torch.bfloat16
+                       else "torch")
         if cache.cu_q is not None:
             # packed chunks (B == 1, S = all rows): one RoPE row per token
             # from its own position, then append and attention over the
@@ -253,15 +278,15 @@ class LlamaGenerator:
             q = F.rope_fwd(q[:, 0], cos, sin)
             k = F.rope_fwd(k[:, 0], cos, sin).unsqueeze(1)
             F.kv_cache_append_paged(k, v, kp, vp, cache.block_table,
-                                    cache.kv_len)
+                                    cache.kv_len, **app)
             o, _ = F.flash_attn_decode(
                 q, kp, vp, cache.kv_len, self.scale, impl=self.decode_impl,
-                block_table=cache.block_table)
+                block_table=cache.block_table, **fp8)
             return o.reshape(B, 1, H * dh) @ wo.t()
         q = F.rope_fwd(q, self.cos[:S], self.sin[:S])
         k = F.rope_fwd(k, self.cos[:S], self.sin[:S])
         F.kv_cache_append_paged(k, v, kp, vp, cache.block_table,
-                                cache.kv_len)
+                                cache.kv_len, **app)
         return self._prefill_attn(q, k.permute(0, 2, 1, 3),
                                   v.permute(0, 2, 1, 3), 0) @ wo.t()
 
@@ -439,7 +464,8 @@ class LlamaGenerator:
         lens = [int(p.numel()) for p in prompts]
         B = len(prompts)
         cache = PagedKVCache(self.cfg, [n + max_new_tokens for n in lens],
-                             self.page_size, self.device, self.dtype)
+                             self.page_size, self.device, self.dtype,
+                             kv_dtype=self.kv_dtype)
         gen = torch.Generator(device="cpu").manual_seed(seed)
         cache.kv_len.copy_(torch.tensor(lens, dtype=torch.int32))
         if self.prefill == "packed":

@@ -756,24 +756,40 @@ def _decode_paged(q, k_pool, v_pool, block_table, kv_len, scale, num_splits,
                   impl, k_scale, v_scale):
     """flash_attn_decode with a block_table (its docstring has the
     contract)."""
-    if k_scale is not None or v_scale is not None \
-            or k_pool.dtype in (_FP8, torch.uint8):
-        raise RuntimeError("flash_attn_decode: block_table with an fp8 cache "
-                           "(k_scale / v_scale): fp8 pools are not supported")
+    fp8 = _decode_paged_is_fp8(k_pool, v_pool, k_scale, v_scale)
     _decode_check_shapes(q, k_pool, v_pool, block_table)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     B, MP = block_table.shape
     L = MP * k_pool.shape[2]
     if not flash_attn_decode_on_hip(q, k_pool, v_pool, kv_len, impl,
-                                    block_table=block_table):
+                                    k_scale, v_scale, block_table):
         if k_pool.shape[0] == 0 or MP == 0:    # no page to gather
             return (q.new_zeros(q.shape),
                     torch.full(q.shape[:2], float("-inf"),
                                dtype=torch.float32, device=q.device))
         kd, vd, n, keep = _decode_paged_gather(k_pool, v_pool, block_table,
                                                kv_len)
+        if fp8:
+            # the scale pools by the same rule (a trailing dim of 1 makes
+            # them pools of one-element rows), then fp32 values
+            ksd, vsd, _, _ = _decode_paged_gather(
+                k_scale.unsqueeze(-1), v_scale.unsqueeze(-1), block_table,
+                kv_len)
+            kd, vd = kd.float() * ksd, vd.float() * vsd
         return _decode_torch(q, kd, vd, n, scale, keep_keys=keep)
+    if fp8:
+        why = _decode_paged_fp8_ineligible(q, k_pool, v_pool, k_scale,
+                                           v_scale, block_table, kv_len)
+        if why is not None:
+            raise RuntimeError(f"flash_attn_decode(impl={impl!r}): {why}")
+        if not isinstance(kv_len, torch.Tensor):
+            kv_len = torch.full((B,), min(max(int(kv_len), 0), L),
+                                dtype=torch.int32, device=q.device)
+        out, lse = ext().flash_attn_decode_paged_fp8(
+            q, k_pool, v_pool, k_scale, v_scale, block_table, kv_len,
+            float(scale), int(num_splits))
+        return out, lse
     why = _decode_paged_ineligible(q, k_pool, v_pool, block_table, kv_len)
     if why is not None:
         raise RuntimeError(f"flash_attn_decode(impl={impl!r}): {why}")
@@ -793,10 +809,12 @@ def _decode_paged(q, k_pool, v_pool, block_table, kv_len, scale, num_splits,
     return out, lse
 
 
-def _decode_is_fp8(k_cache, v_cache, k_scale, v_scale) -> bool:
+def _decode_is_fp8(k_cache, v_cache, k_scale, v_scale,
+                   dims="[B, Hkv, L]") -> bool:
     """Whether the caches are the fp8 format (e4m3 codes, one fp32 scale per
     cached row: value = float(code) * scale[row]); checks that caches and
-    scales go together."""
+    scales go together.  dims names the scales' shape, the caches' first
+    three dims."""
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if t.dtype == torch.uint8:
             raise RuntimeError(
@@ -816,15 +834,26 @@ def _decode_is_fp8(k_cache, v_cache, k_scale, v_scale) -> bool:
     for name, t, cache in scales:
         if t is None:
             raise RuntimeError(f"flash_attn_decode: an fp8 cache needs "
-                               f"{name} (fp32 [B, Hkv, L])")
+                               f"{name} (fp32 {dims})")
         if t.dtype != torch.float32:
             raise RuntimeError(f"flash_attn_decode: {name} is {t.dtype}, "
                                "not float32")
         if tuple(t.shape) != tuple(cache.shape[:3]):
             raise RuntimeError(
                 f"flash_attn_decode: {name} has shape {tuple(t.shape)}, "
-                f"need [B, Hkv, L] = {tuple(cache.shape[:3])}")
+                f"need {dims} = {tuple(cache.shape[:3])}")
     return True
+
+
+def _decode_paged_is_fp8(k_pool, v_pool, k_scale, v_scale) -> bool:
+    """_decode_is_fp8 for page pools: e4m3 code pools [P, Hkv, PS, D] go with
+    fp32 scale pools [P, Hkv, PS]."""
+    if _FP8 in (k_pool.dtype, v_pool.dtype) \
+            and (k_scale is None or v_scale is None):
+        raise RuntimeError("flash_attn_decode: block_table with an fp8 cache "
+                           "needs k_scale and v_scale, the scale pools (fp32 "
+                           "[P, Hkv, PS])")
+    return _decode_is_fp8(k_pool, v_pool, k_scale, v_scale, "[P, Hkv, PS]")
 
 
 def _decode_fp8_ineligible(q, k_cache, v_cache, k_scale, v_scale,
@@ -860,6 +889,25 @@ def _decode_fp8_ineligible(q, k_cache, v_cache, k_scale, v_scale,
     return None
 
 
+def _decode_paged_fp8_ineligible(q, k_pool, v_pool, k_scale, v_scale,
+                                 block_table, kv_len) -> Optional[str]:
+    """Why the PAGED kernel of ops/hip/attention_decode_fp8.hip cannot take
+    this input, or None."""
+    why = _decode_fp8_ineligible(q, k_pool, v_pool, k_scale, v_scale, kv_len)
+    if why is not None:
+        return why
+    if k_pool.shape[2] not in _PAGE_SIZES:
+        return (f"the page size of k_cache / v_cache (dim 2) is "
+                f"{k_pool.shape[2]}, not one of {_PAGE_SIZES}")
+    if not block_table.is_cuda:
+        return "block_table is not on the GPU"
+    if block_table.dtype != torch.int32:
+        return f"block_table is {block_table.dtype}, not int32"
+    if not block_table.is_contiguous():
+        return "block_table is not contiguous"
+    return None
+
+
 def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None,
                              k_scale=None, v_scale=None,
                              block_table=None) -> bool:
@@ -871,6 +919,16 @@ def flash_attn_decode_on_hip(q, k_cache, v_cache, kv_len=0, impl=None,
         return False
     if impl in ("hip", "mfma"):
         return True
+    if block_table is not None and (k_scale is not None
+                                    or k_cache.dtype in (_FP8, torch.uint8)):
+        # fp8 pools: one kernel, and the torch branch is the gather that
+        # _decode_auto_paged_hip's rows lose to the bf16 kernels, plus a
+        # dequantization (not timed)
+        return (_decode_paged_is_fp8(k_cache, v_cache, k_scale, v_scale)
+                and _decode_paged_fp8_ineligible(
+                    q, k_cache, v_cache, k_scale, v_scale, block_table,
+                    kv_len) is None
+                and "fa" not in _TORCH_FB)
     if block_table is not None:
         return (_decode_paged_ineligible(q, k_cache, v_cache, block_table,
                                          kv_len) is None
@@ -931,7 +989,17 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
     impl keeps its meaning ("hip" / "mfma" are the paged variants of the two
     kernels, bit-identical to the dense ones on the same values; "torch"
     gathers the needed pages into a dense cache); the split count comes from
-    B, Hkv, MP * PS and the CU count.  fp8 pools are not supported."""
+    B, Hkv, MP * PS and the CU count.
+
+    fp8 pools: code pools of dtype torch.float8_e4m3fn with k_scale, v_scale
+    fp32 [P, Hkv, PS], the scale pools, also taken with their strides; key j
+    of row b has its code row and its scale at row j % PS of page
+    block_table[b, j // PS] in both, and the value, scale and code
+    definitions are the dense fp8 cache's (F.kv_cache_append_paged writes the
+    format).  One kernel (the PAGED variant of attention_decode_fp8.hip),
+    which None, "hip" and "mfma" all reach, bit-identical to the dense fp8
+    kernel on the same values; "torch" gathers codes and scales and
+    dequantizes in fp32."""
     if impl not in _DECODE_IMPLS:
         raise ValueError("flash_attn_decode: impl must be None, 'torch', "
                          f"'hip' or 'mfma', got {impl!r}")
@@ -976,6 +1044,18 @@ def flash_attn_decode(q, k_cache, v_cache, kv_len, scale=None,
     return out, lse
 
 
+def _quantize_rows_fp8(x):
+    """Rows [..., D] -> (e4m3 codes [..., D], fp32 scales [...]), the fp8 KV
+    cache's definition."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    # a tensor divisor: IEEE division, never a reciprocal multiply
+    s = amax / torch.full_like(amax, 448.0)
+    y = torch.where(s.unsqueeze(-1) == 0, torch.zeros_like(xf),
+                    (xf / s.unsqueeze(-1)).clamp(-448.0, 448.0))
+    return y.to(_FP8), s
+
+
 def _kv_append_fp8_torch(k_new, v_new, k_cache, v_cache, k_scale, v_scale,
                          end):
     """kv_cache_append_fp8 in torch ops, the same definition."""
@@ -986,14 +1066,7 @@ def _kv_append_fp8_torch(k_new, v_new, k_cache, v_cache, k_scale, v_scale,
     bi, si = torch.nonzero((tgt >= 0) & (tgt < L), as_tuple=True)
     ri = tgt[bi, si]
     for x, cache, sc in ((k_new, k_cache, k_scale), (v_new, v_cache, v_scale)):
-        xf = x[bi, si].float()                              # [n, Hkv, D]
-        amax = xf.abs().amax(-1)
-        # a tensor divisor: IEEE division, never a reciprocal multiply
-        s = amax / torch.full_like(amax, 448.0)
-        y = torch.where(s.unsqueeze(-1) == 0, torch.zeros_like(xf),
-                        (xf / s.unsqueeze(-1)).clamp(-448.0, 448.0))
-        cache[bi, :, ri] = y.to(_FP8)
-        sc[bi, :, ri] = s
+        cache[bi, :, ri], sc[bi, :, ri] = _quantize_rows_fp8(x[bi, si])
 
 
 def kv_cache_append_fp8(k_new, v_new, k_cache, v_cache, k_scale, v_scale,
@@ -1066,6 +1139,26 @@ def _kv_append_paged_torch(k_new, v_new, k_pool, v_pool, block_table, end):
         pool[pi, :, ri] = x[bi, si]                            # [n, Hkv, D]
 
 
+def _kv_append_paged_fp8_torch(k_new, v_new, k_pool, v_pool, k_scale, v_scale,
+                               block_table, end):
+    """kv_cache_append_paged into fp8 pools in torch ops:
+    _kv_append_paged_torch's indexing, _kv_append_fp8_torch's quantization."""
+    B, S, Hkv, D = k_new.shape
+    P, PS = k_pool.shape[0], k_pool.shape[2]
+    MP = block_table.shape[1]
+    if MP == 0 or P == 0:
+        return
+    dev = k_new.device
+    tgt = end.to(dev).long().view(B, 1) - S + torch.arange(S, device=dev)
+    slot = torch.div(tgt, PS, rounding_mode="floor").clamp(0, MP - 1)
+    page = block_table.to(dev).long().gather(1, slot)          # [B, S]
+    ok = (tgt >= 0) & (tgt < MP * PS) & (page >= 0) & (page < P)
+    bi, si = torch.nonzero(ok, as_tuple=True)
+    pi, ri = page[bi, si], (tgt % PS)[bi, si]
+    for x, pool, sc in ((k_new, k_pool, k_scale), (v_new, v_pool, v_scale)):
+        pool[pi, :, ri], sc[pi, :, ri] = _quantize_rows_fp8(x[bi, si])
+
+
 def _kv_append_paged_packed_torch(k_new, v_new, k_pool, v_pool, block_table,
                                   end, cu_q):
     """kv_cache_append_paged with cu_q in torch ops, the same definition."""
@@ -1089,7 +1182,8 @@ def _kv_append_paged_packed_torch(k_new, v_new, k_pool, v_pool, block_table,
 
 
 def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
-                          cu_q=None, max_q=None, impl=None):
+                          cu_q=None, max_q=None, impl=None, k_scale=None,
+                          v_scale=None):
     """Copy new K / V rows into a paged KV cache, in place.
 
     k_new, v_new [B, S, Hkv, D], taken with their strides (views into a
@@ -1112,10 +1206,26 @@ def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
     128, 256}), one launch for K and V with position and page read on the
     device (no host sync: capturable); "torch" = the same definition in
     torch ops; None = the kernel on the GPU for 2-byte dtypes, else torch
-    (and with HETU_AMD_TORCH_FALLBACK=fa)."""
+    (and with HETU_AMD_TORCH_FALLBACK=fa).
+
+    fp8 pools: k_pool, v_pool torch.float8_e4m3fn with k_scale, v_scale fp32
+    [P, Hkv, PS] (required; with their strides) take bf16 rows quantized as
+    kv_cache_append_fp8 defines them, code row and scale at the same (page,
+    row); "hip" = the paged kernel of ops/hip/kv_cache_fp8.hip (bf16 input, D
+    64 or 128), None = that kernel on the GPU for bf16 input.  The packed
+    (cu_q) form has no fp8 kernel: an error."""
     if impl not in (None, "torch", "hip"):
         raise ValueError("kv_cache_append_paged: impl must be None, 'torch' "
                          f"or 'hip', got {impl!r}")
+    fp8 = _FP8 in (k_pool.dtype, v_pool.dtype)
+    if fp8 and cu_q is not None:
+        raise RuntimeError("kv_cache_append_paged: cu_q (packed rows) with "
+                           "fp8 pools is not supported: there is no fp8 "
+                           "prefill kernel over the pools yet")
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise RuntimeError(
+            f"kv_cache_append_paged: k_scale / v_scale given with "
+            f"{k_pool.dtype} pools; scales belong to fp8 pools")
     if cu_q is not None:
         if k_new.dim() != 3 or k_new.shape != v_new.shape \
                 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape \
@@ -1154,6 +1264,30 @@ def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, end,
             f"{tuple(k_new.shape)}, {tuple(v_new.shape)}, "
             f"{tuple(k_pool.shape)}, {tuple(v_pool.shape)}, "
             f"{tuple(block_table.shape)}, {tuple(end.shape)}")
+    if fp8:
+        if k_pool.dtype != v_pool.dtype:
+            raise RuntimeError("kv_cache_append_paged: k_pool and v_pool "
+                               "must both be float8_e4m3fn")
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t is None:
+                raise RuntimeError(f"kv_cache_append_paged: fp8 pools need "
+                                   f"{name} (fp32 [P, Hkv, PS])")
+            if t.dtype != torch.float32 \
+                    or tuple(t.shape) != tuple(k_pool.shape[:3]):
+                raise RuntimeError(
+                    f"kv_cache_append_paged: {name} is {t.dtype} "
+                    f"{tuple(t.shape)}, need float32 [P, Hkv, PS] = "
+                    f"{tuple(k_pool.shape[:3])}")
+        if impl is None:
+            impl = "hip" if (k_new.is_cuda and k_new.dtype == torch.bfloat16
+                             and "fa" not in _TORCH_FB) else "torch"
+        if impl == "torch":
+            return _kv_append_paged_fp8_torch(k_new, v_new, k_pool, v_pool,
+                                              k_scale, v_scale, block_table,
+                                              end)
+        ext().kv_cache_append_paged_fp8(k_new, v_new, k_pool, v_pool,
+                                        k_scale, v_scale, block_table, end)
+        return
     if impl is None:
         impl = "hip" if (k_new.is_cuda and k_new.element_size() == 2
                          and "fa" not in _TORCH_FB) else "torch"

@@ -82,9 +82,12 @@ void dec_check_strides(const torch::Tensor& t, const char* what);
 // every TORCH_CHECK of flash_attn_decode, then out / lse / workspace and the
 // kernel arguments; key_tile is the caller's block tile (bounds L).  With a
 // block_table [B, MP] the caches are pools [P, Hkv, PS, D] and L = MP * PS.
+// fp8: the caches hold e4m3 codes, strides are bytes and the caller checks
+// them (attention_decode_fp8.hip).
 DecCall dec_prepare(const torch::Tensor& q, const torch::Tensor& k_cache,
                     const torch::Tensor& v_cache, const torch::Tensor& kv_len,
                     double scale, int64_t num_splits, int key_tile,
-                    const torch::Tensor* block_table = nullptr);
+                    const torch::Tensor* block_table = nullptr,
+                    bool fp8 = false);
 // fa_decode_merge_kernel over the [B, H, ns, D + 1] workspace (ns > 1 only)
 void dec_merge_launch(const DecCall& c, hipStream_t stream);

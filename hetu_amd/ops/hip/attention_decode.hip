@@ -92,7 +92,7 @@ int64_t decode_attn_num_splits(int64_t B, int64_t Hkv, int64_t L,
 DecCall dec_prepare(const torch::Tensor& q, const torch::Tensor& k_cache,
                     const torch::Tensor& v_cache, const torch::Tensor& kv_len,
                     double scale, int64_t num_splits, int key_tile,
-                    const torch::Tensor* block_table) {
+                    const torch::Tensor* block_table, bool fp8) {
   const bool paged = block_table != nullptr;
   TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda() &&
               kv_len.is_cuda(),
@@ -104,10 +104,13 @@ DecCall dec_prepare(const torch::Tensor& q, const torch::Tensor& k_cache,
   TORCH_CHECK(!paged || (block_table->is_cuda() &&
                          block_table->device() == q.device()),
               "flash_attn_decode: block_table must be on q's GPU");
+  const auto cache_type = fp8 ? at::kFloat8_e4m3fn : at::kBFloat16;
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 &&
-              k_cache.scalar_type() == at::kBFloat16 &&
-              v_cache.scalar_type() == at::kBFloat16,
-              "flash_attn_decode: q, k_cache and v_cache must be bf16");
+              k_cache.scalar_type() == cache_type &&
+              v_cache.scalar_type() == cache_type,
+              fp8 ? "flash_attn_decode (fp8 cache): q must be bf16, k_cache "
+                    "and v_cache float8_e4m3fn"
+                  : "flash_attn_decode: q, k_cache and v_cache must be bf16");
   TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4,
               "flash_attn_decode: need q [B, H, D] and caches "
               "[B, Hkv, L, D] (pools [P, Hkv, PS, D] with a block_table)");
@@ -151,8 +154,10 @@ DecCall dec_prepare(const torch::Tensor& q, const torch::Tensor& k_cache,
   c.empty = B == 0 || H == 0;
   if (c.empty) return c;
   dec_check_strides(q, "q");
-  dec_check_strides(k_cache, "k_cache");
-  dec_check_strides(v_cache, "v_cache");
+  if (!fp8) {
+    dec_check_strides(k_cache, "k_cache");
+    dec_check_strides(v_cache, "v_cache");
+  }
 
   const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
   const int ns = (int)(num_splits > 0

@@ -48,9 +48,26 @@
 // valid key before they become addresses, for the scale loads too (a clamped
 // row is valid, so its scale must be: 0 * NaN is NaN); a score past the end
 // is selected to -inf and its p to 0.
+//
+// PAGED (flash_attn_decode_paged_fp8): k / v are code pools [P, Hkv, PS, D]
+// and the scales pools [P, Hkv, PS] behind a block table (attention_decode.h).
+// A wave's 32 keys of a tile are aligned to 32 and PS >= 32, so its two K
+// loads, its four 16-byte scale loads and its V image come from one page: one
+// scalar id per wave and tile offsets all four pools; rows are clamped as
+// above (a clamped key stays in the wave's own 32 keys, so in the page the id
+// was read for) and then reduced mod PS.  Ids run two tiles ahead as in the
+// paged MFMA kernel: the trip of tile i stages V(i + 1) and reloads K(i + 1)
+// and its scales with the id it already holds, and requests the id of tile
+// i + 2.  A page id outside [0, P) is 32 masked keys: nothing is loaded for
+// the tile and its compute is skipped, wave-uniformly (a stale image or stale
+// registers may hold NaN, and 0 x NaN is NaN in an MFMA); the loop head then
+// drains instead of counting a DMA that was not issued.  Same tiles, streams
+// and merge order as the dense kernel: bit-identical results for the same
+// values.
 #include <ATen/hip/HIPContext.h>
 #include "ext_stream.h"
 #include "attention_common.h"
+#include <type_traits>
 #include "attention_decode.h"
 
 namespace {
@@ -70,13 +87,18 @@ constexpr int D8_PP = 3;                       // bf16 parts of P: 24 bits
 constexpr int D8_MAX_MT = 2;
 static_assert(D8_BN % DEC_BN == 0, "tiles are whole split units");
 
-struct Dec8Args {
-  DecArgs a;                  // a.k, a.v: the code bytes, strides in bytes
+// A = DecPagedArgs: a.k / a.v are the code pools, ks / vs the scale pools
+// [P, Hkv, PS] and every *_bs a page stride
+template <class A>
+struct Dec8ArgsT {
+  A a;                        // a.k, a.v: the code bytes, strides in bytes
   const float* ks;            // [B, Hkv, L], last dim contiguous
   const float* vs;
   long long ks_bs, ks_hs, vs_bs, vs_hs;
   int ks_vec, vs_vec;         // every (b, hkv) row of scales is 16-B aligned
 };
+using Dec8Args = Dec8ArgsT<DecArgs>;
+using Dec8PagedArgs = Dec8ArgsT<DecPagedArgs>;
 
 template <int D>
 DEV int d8_swz(int row) {
@@ -95,10 +117,11 @@ DEV bf16x8 d8_cvt8(unsigned lo, unsigned hi) {
   return u.v;
 }
 
-// stage keys k0 .. k0 + 31 (clamped to klast) of V into a wave's image
+// stage keys k0 .. k0 + 31 (clamped to klast) of V into a wave's image; a
+// row index is taken & rmask (-1: dense; PS - 1: the row within vb's page)
 template <int D>
 DEV void d8_stage_v(const u8* vb, long long v_rs, int k0, int klast,
-                    char* img, int lane) {
+                    int rmask, char* img, int lane) {
 #pragma unroll
   for (int i = 0; i < D8_WKEYS * D / 1024; ++i) {
     const int pos = (i * WAVE + lane) * 16;
@@ -106,7 +129,7 @@ DEV void d8_stage_v(const u8* vb, long long v_rs, int k0, int klast,
     const int col = (pos % D) ^ (d8_swz<D>(row) << 4);
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) void*)(
-            vb + (int64_t)min(k0 + row, klast) * v_rs + col),
+            vb + (int64_t)(min(k0 + row, klast) & rmask) * v_rs + col),
         (__attribute__((address_space(3))) void*)(img + pos), 16, 0, 0);
   }
 }
@@ -115,11 +138,11 @@ DEV void d8_stage_v(const u8* vb, long long v_rs, int k0, int klast,
 // 64 kl + 16 g .. + 16
 template <int D>
 DEV void d8_load_k(uint4 (&kr)[2][D / 64], const u8* kb, long long k_rs,
-                   int k0, int klast, int lane) {
+                   int k0, int klast, int rmask, int lane) {
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const u8* row = kb + (int64_t)min(k0 + 16 * c + (lane & 15), klast) *
-                             k_rs + 16 * (lane >> 4);
+    const u8* row = kb + (int64_t)(min(k0 + 16 * c + (lane & 15), klast) &
+                                   rmask) * k_rs + 16 * (lane >> 4);
 #pragma unroll
     for (int kl = 0; kl < D / 64; ++kl)
       kr[c][kl] = *reinterpret_cast<const uint4*>(row + 64 * kl);
@@ -128,16 +151,30 @@ DEV void d8_load_k(uint4 (&kr)[2][D / 64], const u8* kb, long long k_rs,
 
 // the scales of keys kb .. kb + 3 (kb a multiple of 4), each index clamped
 // to klast: one 16-byte load where all four are valid and the row of scales
-// is aligned, else four clamped loads
-DEV f32x4 d8_load_scale(const float* sb, int kb, int klast, bool vec) {
+// is aligned, else four clamped loads; indices & rmask as above (four keys
+// from a multiple of 4 never straddle a page)
+DEV f32x4 d8_load_scale(const float* sb, int kb, int klast, int rmask,
+                        bool vec) {
   f32x4 r;
   if (vec && kb + 3 <= klast) {
-    r = *reinterpret_cast<const f32x4*>(sb + kb);
+    r = *reinterpret_cast<const f32x4*>(sb + (kb & rmask));
   } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = sb[min(kb + j, klast)];
+    for (int j = 0; j < 4; ++j) r[j] = sb[min(kb + j, klast) & rmask];
   }
   return r;
+}
+
+// the scales of the wave's 32 keys from k0: keys 16 c + 4 lg + r
+DEV void d8_load_scales(f32x4 (&ksc)[2], f32x4 (&vsc)[2], const float* ksb,
+                        const float* vsb, int k0, int klast, int rmask,
+                        bool ks_vec, bool vs_vec, int lg) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int kn = k0 + 16 * c + 4 * lg;
+    ksc[c] = d8_load_scale(ksb, kn, klast, rmask, ks_vec);
+    vsc[c] = d8_load_scale(vsb, kn, klast, rmask, vs_vec);
+  }
 }
 
 // V^T A fragments of d blocks db0 .. db0 + 3 (row d = 16 db + i, slots = the
@@ -167,9 +204,10 @@ DEV void d8_tr_v4(bf16x8 (&vt)[4], const char* img, int db0, int lane) {
 
 // two blocks per CU wherever that compiles without scratch: all but D = 128
 // with two head tiles
-template <int D, int MT>
+template <int D, int MT, bool PAGED = false>
 __global__ __launch_bounds__(D8_THREADS, (D == 128 && MT >= 2) ? 1 : 2)
-void fa_decode_fp8_kernel(Dec8Args ar) {
+void fa_decode_fp8_kernel(
+    std::conditional_t<PAGED, Dec8PagedArgs, Dec8Args> ar) {
   constexpr int IMG = D8_WKEYS * D;            // 4 KiB (D = 128) / 2 KiB
   constexpr int NV = IMG / 1024;               // DMA instructions per tile
   constexpr int KL = D / 64;                   // 16-byte K loads per row
@@ -183,7 +221,7 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
   __shared__ __attribute__((aligned(1024))) char
       smem[RING_BYTES > MERGE_BYTES ? RING_BYTES : MERGE_BYTES];
 
-  const DecArgs& a = ar.a;
+  const auto& a = ar.a;
   const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
   const int G = a.H / a.Hkv;
   const int ns = a.ns;
@@ -213,12 +251,34 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hi = lane & 15;            // head column / key row of a fragment
   const int lg = lane >> 4;            // lane group
-  const u8* kb = reinterpret_cast<const u8*>(a.k) + (int64_t)b * a.k_bs +
-                 (int64_t)hkv * a.k_hs;
-  const u8* vb = reinterpret_cast<const u8*>(a.v) + (int64_t)b * a.v_bs +
-                 (int64_t)hkv * a.v_hs;
-  const float* ksb = ar.ks + (int64_t)b * ar.ks_bs + (int64_t)hkv * ar.ks_hs;
-  const float* vsb = ar.vs + (int64_t)b * ar.vs_bs + (int64_t)hkv * ar.vs_hs;
+  // dense: the batch row's caches and scales; paged: the pools, the *page
+  // lambdas add the page
+  const u8* kb = reinterpret_cast<const u8*>(a.k) +
+                 (PAGED ? 0 : (int64_t)b * a.k_bs) + (int64_t)hkv * a.k_hs;
+  const u8* vb = reinterpret_cast<const u8*>(a.v) +
+                 (PAGED ? 0 : (int64_t)b * a.v_bs) + (int64_t)hkv * a.v_hs;
+  const float* ksb = ar.ks + (PAGED ? 0 : (int64_t)b * ar.ks_bs) +
+                     (int64_t)hkv * ar.ks_hs;
+  const float* vsb = ar.vs + (PAGED ? 0 : (int64_t)b * ar.vs_bs) +
+                     (int64_t)hkv * ar.vs_hs;
+  const auto kpage = [&](int page) {
+    if constexpr (PAGED) return kb + (int64_t)page * a.k_bs;
+    else return kb;
+  };
+  const auto vpage = [&](int page) {
+    if constexpr (PAGED) return vb + (int64_t)page * a.v_bs;
+    else return vb;
+  };
+  const auto kspage = [&](int page) {
+    if constexpr (PAGED) return ksb + (int64_t)page * ar.ks_bs;
+    else return ksb;
+  };
+  const auto vspage = [&](int page) {
+    if constexpr (PAGED) return vsb + (int64_t)page * ar.vs_bs;
+    else return vsb;
+  };
+  int rmask = -1;                      // row within the page
+  if constexpr (PAGED) rmask = (1 << a.ps_shift) - 1;
   const bool ks_vec = ar.ks_vec != 0, vs_vec = ar.vs_vec != 0;
   const float scale = a.scale;
   // this split's keys; every address is clamped to klast < kv <= L
@@ -260,23 +320,56 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
 
     uint4 kr[2][KL];
     f32x4 ksc[2], vsc[2];              // scales of keys 16 c + 4 lg + r
-    if (nt > 0) {
-      d8_load_k<D>(kr, kb, a.k_rs, kw0, klast, lane);
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        ksc[c] = d8_load_scale(ksb, kw0 + 16 * c + 4 * lg, klast, ks_vec);
-        vsc[c] = d8_load_scale(vsb, kw0 + 16 * c + 4 * lg, klast, vs_vec);
+    // paged: the page id of tile i + 1 and whether tile i has a page at all
+    // (dense: no ids, every tile has)
+    [[maybe_unused]] int page_nx = 0;
+    bool ok = true;
+    if constexpr (PAGED) {
+      const int page = dec_page_of(a, b, min(kw0, klast));
+      page_nx = dec_page_of(a, b, min(kw0 + D8_BN, klast));
+      ok = (unsigned)page < (unsigned)a.P;
+      if (nt > 0 && ok) {
+        d8_load_k<D>(kr, kpage(page), a.k_rs, kw0, klast, rmask, lane);
+        d8_load_scales(ksc, vsc, kspage(page), vspage(page), kw0, klast,
+                       rmask, ks_vec, vs_vec, lg);
+        d8_stage_v<D>(vpage(page), a.v_rs, kw0, klast, rmask, ring, lane);
       }
-      d8_stage_v<D>(vb, a.v_rs, kw0, klast, ring, lane);
+    } else if (nt > 0) {
+      d8_load_k<D>(kr, kb, a.k_rs, kw0, klast, rmask, lane);
+      d8_load_scales(ksc, vsc, ksb, vsb, kw0, klast, rmask, ks_vec, vs_vec,
+                     lg);
+      d8_stage_v<D>(vb, a.v_rs, kw0, klast, rmask, ring, lane);
     }
     for (int i = 0; i < nt; ++i) {     // wave-uniform trip count
       const int k0 = kw0 + i * D8_BN;
       const bool last = i + 1 == nt;
       const char* img = ring + (i & 1) * IMG;
-      if (!last)
-        d8_stage_v<D>(vb, a.v_rs, k0 + D8_BN, klast,
+      bool more = !last;               // tile i + 1 is loaded in this trip
+      [[maybe_unused]] int page_nn = 0;
+      if constexpr (PAGED) {
+        // tile i + 2's id: first used one trip from here
+        int key_nn = min(k0 + 2 * D8_BN, klast);
+        dec_page_landed(page_nx, key_nn);
+        page_nn = dec_page_of(a, b, key_nn);
+        more = !last && (unsigned)page_nx < (unsigned)a.P;
+      }
+      if (more)
+        d8_stage_v<D>(vpage(page_nx), a.v_rs, k0 + D8_BN, klast, rmask,
                       ring + ((i + 1) & 1) * IMG, lane);
-      fa_wait_tile<NV>(last);          // K(i), scales(i) and V(i) are in
+      if constexpr (PAGED) {
+        if (!ok) {                     // 32 masked keys: nothing was loaded
+          if (more) {
+            d8_load_k<D>(kr, kpage(page_nx), a.k_rs, k0 + D8_BN, klast,
+                         rmask, lane);
+            d8_load_scales(ksc, vsc, kspage(page_nx), vspage(page_nx),
+                           k0 + D8_BN, klast, rmask, ks_vec, vs_vec, lg);
+          }
+          page_nx = page_nn;
+          ok = more;
+          continue;
+        }
+      }
+      fa_wait_tile<NV>(!more);         // K(i), scales(i) and V(i) are in
       __builtin_amdgcn_sched_barrier(0);   // no MFMA above the DMA issue
 
       f32x4 s[MT][2];
@@ -297,7 +390,9 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
           }
         }
       }
-      if (!last) d8_load_k<D>(kr, kb, a.k_rs, k0 + D8_BN, klast, lane);
+      if (more)
+        d8_load_k<D>(kr, kpage(page_nx), a.k_rs, k0 + D8_BN, klast, rmask,
+                     lane);
 
       // lane (lg, hi) holds keys k0 + 16 c + 4 lg + r of head hi; the tile's
       // first key is valid, so every head's new maximum is finite
@@ -347,14 +442,9 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[mt][db][r] *= alpha;
       }
-      if (!last) {                     // the scales are consumed: reload
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int kn = k0 + D8_BN + 16 * c + 4 * lg;
-          ksc[c] = d8_load_scale(ksb, kn, klast, ks_vec);
-          vsc[c] = d8_load_scale(vsb, kn, klast, vs_vec);
-        }
-      }
+      if (more)                        // the scales are consumed: reload
+        d8_load_scales(ksc, vsc, kspage(page_nx), vspage(page_nx),
+                       k0 + D8_BN, klast, rmask, ks_vec, vs_vec, lg);
 
 #pragma unroll
       for (int q4 = 0; q4 < NDB / 4; ++q4) {
@@ -369,6 +459,10 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
               acc[mt][4 * q4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                   vt[j], pf[mt][t], acc[mt][4 * q4 + j], 0, 0, 0);
       }
+      if constexpr (PAGED) {
+        page_nx = page_nn;
+        ok = more;
+      }
     }
 
     // the wave's stream: l over the lane groups (m is already common)
@@ -379,7 +473,8 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
     }
     // merge the waves in wave order, one head tile at a time, through the
     // bytes of the rings; thread = (head of the tile, DPT dims).  The split
-    // is not empty, so wave 0 met a valid key: mx is finite.
+    // is not empty, so wave 0 met a valid key: mx is finite (paged: unless
+    // every page of the split is out of range; patched below).
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       __syncthreads();                 // rings / the previous tile are done
@@ -414,7 +509,17 @@ void fa_decode_fp8_kernel(Dec8Args ar) {
 #pragma unroll
         for (int j = 0; j < DPT; ++j) o[j] *= inv;
         const int64_t row = row0 + head;
-        const float ls = mx + logf(lt);
+        float ls = mx + logf(lt);
+        // no loaded key: replace the NaN of exp(-inf + inf) after the fact,
+        // so that the sums above stay the dense kernel's, operation for
+        // operation
+        if constexpr (PAGED) {
+          if (mx == -INFINITY) {
+            ls = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < DPT; ++j) o[j] = 0.f;
+          }
+        }
         if (ns == 1) {
           bf16* dst = a.out + row * D + d0;
 #pragma unroll
@@ -449,15 +554,16 @@ void d8_check_cache(const torch::Tensor& t, const char* what) {
               what, " is not 16-byte aligned");
 }
 
-// checks a scale tensor; returns whether every (b, hkv) row is 16-B aligned
+// checks a scale tensor (`shape` names the cache's first three dims); returns
+// whether every (b, hkv) / (page, hkv) row is 16-B aligned
 bool d8_check_scale(const torch::Tensor& s, const torch::Tensor& cache,
-                    const char* what) {
+                    const char* what, const char* shape = "[B, Hkv, L]") {
   TORCH_CHECK(s.is_cuda() && s.device() == cache.device(), D8_FN, what,
               " must be on the caches' device");
   TORCH_CHECK(s.scalar_type() == at::kFloat, D8_FN, what, " must be fp32");
   TORCH_CHECK(s.dim() == 3 && s.size(0) == cache.size(0) &&
               s.size(1) == cache.size(1) && s.size(2) == cache.size(2),
-              D8_FN, what, " must be [B, Hkv, L]");
+              D8_FN, what, " must be ", shape);
   TORCH_CHECK(s.size(2) == 1 || s.stride(2) == 1, D8_FN, what,
               " needs a contiguous last dim");
   bool vec = reinterpret_cast<uintptr_t>(s.data_ptr()) % 16 == 0;
@@ -559,5 +665,44 @@ std::vector<torch::Tensor> flash_attn_decode_fp8(
 #undef D8_LAUNCH
   HIP_CHECK(hipGetLastError());
   if (a.ns > 1) dec_merge_launch(c, stream);
+  return {c.out, c.lse};
+}
+
+std::vector<torch::Tensor> flash_attn_decode_paged_fp8(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor block_table,
+    torch::Tensor kv_len, double scale, int64_t num_splits) {
+  // the id prefetch forms keys up to two tiles past the last one
+  DecCall c = dec_prepare(q, k_pool, v_pool, kv_len, scale, num_splits,
+                          3 * D8_BN, &block_table, /*fp8=*/true);
+  if (c.empty) return {c.out, c.lse};
+  d8_check_cache(k_pool, "k_pool");
+  d8_check_cache(v_pool, "v_pool");
+  Dec8PagedArgs ar;
+  ar.ks_vec = d8_check_scale(k_scale, k_pool, "k_scale", "[P, Hkv, PS]");
+  ar.vs_vec = d8_check_scale(v_scale, v_pool, "v_scale", "[P, Hkv, PS]");
+  ar.a = c.paged();
+  ar.ks = k_scale.data_ptr<float>();
+  ar.vs = v_scale.data_ptr<float>();
+  ar.ks_bs = k_scale.stride(0); ar.ks_hs = k_scale.stride(1);
+  ar.vs_bs = v_scale.stride(0); ar.vs_hs = v_scale.stride(1);
+  const int64_t G = c.H / c.Hkv;
+  const int mt = G <= 16 ? 1 : D8_MAX_MT;
+  auto stream = hetu_current_stream();
+  const dim3 grid(ar.a.ns, (unsigned)c.Hkv, (unsigned)c.B);
+#define D8_LAUNCH(DD, MM)                                                  \
+  hipLaunchKernelGGL((fa_decode_fp8_kernel<DD, MM, true>), grid,           \
+                     dim3(D8_THREADS), 0, stream, ar)
+#define D8_LAUNCH_D(DD)                                                    \
+  do {                                                                     \
+    if (mt == 1) D8_LAUNCH(DD, 1);                                         \
+    else D8_LAUNCH(DD, D8_MAX_MT);                                         \
+  } while (0)
+  if (c.D == 128) D8_LAUNCH_D(128);
+  else D8_LAUNCH_D(64);
+#undef D8_LAUNCH_D
+#undef D8_LAUNCH
+  HIP_CHECK(hipGetLastError());
+  if (ar.a.ns > 1) dec_merge_launch(c, stream);
   return {c.out, c.lse};
 }

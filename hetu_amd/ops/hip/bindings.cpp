@@ -195,11 +195,19 @@ std::vector<torch::Tensor> flash_attn_decode_fp8(
     torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor kv_len,
     double scale, int64_t num_splits);
+std::vector<torch::Tensor> flash_attn_decode_paged_fp8(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor block_table,
+    torch::Tensor kv_len, double scale, int64_t num_splits);
 // kv_cache_fp8.hip
 void kv_cache_append_fp8(torch::Tensor k_new, torch::Tensor v_new,
                          torch::Tensor k_cache, torch::Tensor v_cache,
                          torch::Tensor k_scale, torch::Tensor v_scale,
                          torch::Tensor end);
+void kv_cache_append_paged_fp8(torch::Tensor k_new, torch::Tensor v_new,
+                               torch::Tensor k_pool, torch::Tensor v_pool,
+                               torch::Tensor k_scale, torch::Tensor v_scale,
+                               torch::Tensor block_table, torch::Tensor end);
 
 // embed_cache.cpp
 void register_embed_cache(pybind11::module& m);
@@ -285,6 +293,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"),
         py::arg("num_splits") = 0);
   m.def("kv_cache_append_fp8", &kv_cache_append_fp8);
+  m.def("flash_attn_decode_paged_fp8", &flash_attn_decode_paged_fp8,
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+        py::arg("kv_len"), py::arg("scale"), py::arg("num_splits") = 0);
+  m.def("kv_cache_append_paged_fp8", &kv_cache_append_paged_fp8);
   m.def("flash_attn_decode_paged", &flash_attn_decode_paged, py::arg("q"),
         py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
         py::arg("kv_len"), py::arg("scale"), py::arg("num_splits") = 0);
