@@ -21,6 +21,14 @@ prefill_chunk tokens that attend the context already cached.  kv_dtype="fp8"
 makes the pages e4m3 codes with one fp32 scale per cached row (prefill=
 "sequence" only: the prefill attends the bf16 rows it just computed).
 
+generate(speculative=k) on the paged cache decodes greedily with up to k
+drafted tokens per sequence and step: the chunk [last accepted token] + drafts
+of every live sequence goes through one packed forward (the split-KV
+verification kernel, F.flash_attn_prefill_paged(impl="split"), where it is
+eligible), the longest draft prefix that equals the model's own argmax chain
+is accepted and one more token comes for free.  The output is plain greedy
+decoding's; a step that accepts drafts reads the cache once for several tokens.
+
 Weights load from a hetu_amd checkpoint dir (utils/checkpoint format,
 incl. checkpoints converted from HF with utils/hf_convert) or from an
 in-memory state dict.
@@ -59,6 +67,21 @@ def sample_next(logits: torch.Tensor, temperature: float = 0.0,
     probs = torch.softmax(lg, dim=-1).cpu()
     return torch.multinomial(probs, 1, generator=gen).squeeze(-1) \
         .to(logits.device)
+
+
+def prompt_lookup_draft(tokens: torch.Tensor, k: int) -> torch.Tensor:
+    """Drafts without a draft model: up to k tokens that followed the most
+    recent earlier occurrence of the sequence's last two tokens; nothing if
+    they never occurred before."""
+    n = tokens.numel()
+    if n < 3:
+        return tokens[:0]
+    at = ((tokens[:-2] == tokens[-2]) & (tokens[1:-1] == tokens[-1])) \
+        .nonzero()
+    if not at.numel():
+        return tokens[:0]
+    i = int(at[-1]) + 2
+    return tokens[i:i + k]
 
 
 class LlamaKVCache:
@@ -140,14 +163,16 @@ class PagedKVCache:
         self.kv_len = torch.zeros(len(need), device=device, dtype=torch.int32)
         self.cu_q = None               # set by packed(): a packed forward
 
-    def packed(self, cu_q, max_q: int, pos) -> "PagedKVCache":
+    def packed(self, cu_q, max_q: int, pos,
+               split: bool = False) -> "PagedKVCache":
         """The same cache for one packed forward of ragged chunks: cu_q int32
         [B + 1] bounds the chunks in the packed rows, max_q is the longest,
         pos [T] each row's position; kv_len already holds the lengths after
-        the chunks."""
+        the chunks.  split: short chunks behind long contexts, for the
+        split-KV verification kernel."""
         one = object.__new__(PagedKVCache)
         one.__dict__.update(self.__dict__)
-        one.cu_q, one.max_q, one.pos = cu_q, max_q, pos
+        one.cu_q, one.max_q, one.pos, one.split = cu_q, max_q, pos, split
         return one
 
     def row(self, b: int) -> "PagedKVCache":
@@ -266,9 +291,16 @@ class LlamaGenerator:
             F.kv_cache_append_paged(k, v[0], kp, vp, cache.block_table,
                                     cache.kv_len, cu_q=cache.cu_q,
                                     max_q=cache.max_q)
+            # verification chunks take the split-KV kernel where it is
+            # eligible (and HETU_AMD_TORCH_FALLBACK=fa does not ask for torch:
+            # an explicit impl would bypass that switch), else today's path
+            split = cache.split and "fa" not in F._TORCH_FB and \
+                F._prefill_paged_ineligible(q, kp, vp, cache.block_table,
+                                            cache.cu_q, cache.kv_len) is None
             o, _ = F.flash_attn_prefill_paged(
                 q, kp, vp, cache.block_table, cache.cu_q, cache.kv_len,
-                self.scale, max_q=cache.max_q)
+                self.scale, max_q=cache.max_q,
+                impl="split" if split else None)
             return o.reshape(1, S, H * dh) @ wo.t()
         if S == 1:
             # one RoPE row per sequence, gathered from its own position; the
@@ -395,6 +427,25 @@ class LlamaGenerator:
         x = self._hidden(ids, cache, pos0)
         return x[:, -1] @ self.w["lm_head.weight"].t()   # last-token logits
 
+    def _packed_hidden(self, chunks, starts, cache: PagedKVCache,
+                       split: bool = False):
+        """One packed forward over the paged cache: chunks[b] (1-D ids, may be
+        empty) stands at positions starts[b] .. of sequence b, behind the
+        context already cached; kv_len is set to the lengths after the
+        chunks.  -> (the final-norm rows [T, hidden], cu: chunk b is rows
+        cu[b] .. cu[b + 1])."""
+        ns = [int(c.numel()) for c in chunks]
+        cu = [0]
+        for n in ns:
+            cu.append(cu[-1] + n)
+        cache.kv_len.copy_(torch.tensor([s + n for s, n in zip(starts, ns)],
+                                        dtype=torch.int32))
+        pos = torch.cat([torch.arange(s, s + n) for s, n in zip(starts, ns)])
+        view = cache.packed(
+            torch.tensor(cu, dtype=torch.int32).to(self.device), max(ns),
+            pos.to(self.device), split)
+        return self._hidden(torch.cat(chunks).unsqueeze(0), view, None)[0], cu
+
     def _prefill_packed(self, prompts, lens, cache: PagedKVCache):
         """All prompts through packed forwards over the paged cache, in
         rounds of at most prefill_chunk tokens per sequence (one round
@@ -406,16 +457,8 @@ class LlamaGenerator:
         for done in range(0, max(lens, default=0), max(step, 1)):
             lo = [min(done, n) for n in lens]
             hi = [min(done + step, n) for n in lens]
-            cu = [0]
-            for a, e in zip(lo, hi):
-                cu.append(cu[-1] + e - a)
-            cache.kv_len.copy_(torch.tensor(hi, dtype=torch.int32))
-            ids = torch.cat([p[a:e] for p, a, e in zip(prompts, lo, hi)])
-            pos = torch.cat([torch.arange(a, e) for a, e in zip(lo, hi)])
-            view = cache.packed(
-                torch.tensor(cu, dtype=torch.int32).to(self.device),
-                max(e - a for a, e in zip(lo, hi)), pos.to(self.device))
-            x = self._hidden(ids.unsqueeze(0), view, None)[0]
+            x, cu = self._packed_hidden(
+                [p[a:e] for p, a, e in zip(prompts, lo, hi)], lo, cache)
             for b in range(B):
                 if lo[b] < hi[b] == lens[b]:       # held its last token
                     logits[b] = x[cu[b + 1] - 1]
@@ -426,10 +469,35 @@ class LlamaGenerator:
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,
                  temperature: float = 0.0, top_k: int = 0,
                  top_p: float = 0.0, eos_id: Optional[int] = None,
-                 seed: int = 0) -> torch.Tensor:
+                 seed: int = 0, speculative: Optional[int] = None,
+                 draft=None) -> torch.Tensor:
         """input_ids [B, S] -> [B, S + new]; temperature 0 = greedy.  With
         kv_layout="paged" also a list of 1-D prompts of unequal length -> a
-        list of 1-D outputs, each cut after its first eos_id."""
+        list of 1-D outputs, each cut after its first eos_id.
+
+        speculative=k: greedy decoding that verifies up to k drafted tokens
+        per sequence and step (kv_layout="paged", temperature 0, bf16 / fp32
+        pages); the tokens are those of speculative=None.  draft(tokens, k)
+        -> up to k proposed next tokens of the 1-D sequence so far (tensor or
+        list, may be empty); default: prompt lookup (prompt_lookup_draft)."""
+        if speculative is not None:
+            if int(speculative) < 1:
+                raise ValueError("speculative must be None or a positive "
+                                 f"draft length, got {speculative!r}")
+            if self.kv_layout != "paged":
+                raise ValueError("speculative decoding needs kv_layout="
+                                 f"'paged', got {self.kv_layout!r}")
+            if temperature > 0:
+                raise ValueError("speculative decoding is greedy: "
+                                 f"temperature must be 0, got {temperature}")
+            if self.kv_dtype is not None:
+                raise ValueError("speculative decoding needs bf16 / fp32 "
+                                 f"pages, got kv_dtype={self.kv_dtype!r}")
+            return self._generate_speculative(
+                input_ids, max_new_tokens, eos_id, int(speculative),
+                draft or prompt_lookup_draft)
+        if draft is not None:
+            raise ValueError("draft needs speculative=k")
         if self.kv_layout == "paged":
             return self._generate_paged(input_ids, max_new_tokens,
                                         temperature, top_k, top_p, eos_id,
@@ -457,16 +525,14 @@ class LlamaGenerator:
         return torch.cat(out, dim=1)
 
 
-    def _generate_paged(self, input_ids, max_new_tokens, temperature, top_k,
-                        top_p, eos_id, seed):
-        ragged = not isinstance(input_ids, torch.Tensor)
+    def _prefill_paged(self, input_ids, extra):
+        """The prompts into a fresh paged cache with room for `extra` more
+        tokens each -> (prompts, lens, cache, last-token logits)."""
         prompts = [p.to(self.device).view(-1) for p in input_ids]
         lens = [int(p.numel()) for p in prompts]
-        B = len(prompts)
-        cache = PagedKVCache(self.cfg, [n + max_new_tokens for n in lens],
+        cache = PagedKVCache(self.cfg, [n + extra for n in lens],
                              self.page_size, self.device, self.dtype,
                              kv_dtype=self.kv_dtype)
-        gen = torch.Generator(device="cpu").manual_seed(seed)
         cache.kv_len.copy_(torch.tensor(lens, dtype=torch.int32))
         if self.prefill == "packed":
             logits = self._prefill_packed(prompts, lens, cache)
@@ -474,6 +540,62 @@ class LlamaGenerator:
             # one sequence at a time through the dense prefill path
             logits = torch.cat([self._forward(p.unsqueeze(0), cache.row(b), 0)
                                 for b, p in enumerate(prompts)])
+        return prompts, lens, cache, logits
+
+    def _generate_speculative(self, input_ids, max_new_tokens, eos_id, k,
+                              draft):
+        ragged = not isinstance(input_ids, torch.Tensor)
+        # a chunk may write k rejected rows past the last token that counts
+        prompts, lens, cache, logits = self._prefill_paged(
+            input_ids, max_new_tokens + k)
+        B = len(prompts)
+        if max_new_tokens < 1:
+            return prompts if ragged else torch.stack(prompts)
+        # new[b]: the tokens generated so far; all but the last are cached
+        new = [[t] for t in logits.argmax(-1).tolist()]
+        lm_head = self.w["lm_head.weight"]
+
+        def want():
+            # as _generate_paged: a ragged sequence ends at its eos, a
+            # rectangular batch runs until every row has met one
+            end = [n.index(eos_id) + 1 if eos_id is not None and eos_id in n
+                   else max_new_tokens for n in new]
+            return end if ragged else [max(end)] * B
+        while any(alive := [len(n) < w for n, w in zip(new, want())]):
+            chunks = []
+            for b in range(B):
+                d = []
+                room = min(k, max_new_tokens - len(new[b]) - 1)
+                if alive[b] and room > 0:
+                    seq = torch.cat([prompts[b], torch.tensor(
+                        new[b], device=self.device)])
+                    d = torch.as_tensor(draft(seq, room)).view(-1)[:room] \
+                        .tolist()
+                chunks.append(torch.tensor(
+                    (new[b][-1:] + d) if alive[b] else [], dtype=torch.long,
+                    device=self.device))
+            starts = [n + len(t) - 1 for n, t in zip(lens, new)]
+            x, cu = self._packed_hidden(chunks, starts, cache, split=True)
+            pred = (x @ lm_head.t()).argmax(-1).tolist()
+            for b in range(B):
+                if not alive[b]:
+                    continue
+                d, p = chunks[b].tolist()[1:], pred[cu[b]:cu[b + 1]]
+                a = 0                  # the accepted drafts, then p[a] free
+                while a < len(d) and d[a] == p[a]:
+                    a += 1
+                new[b] += d[:a] + [p[a]]
+        out = [torch.cat([p, torch.tensor(n[:w], device=self.device)])
+               for p, n, w in zip(prompts, new, want())]
+        return out if ragged else torch.stack(out)
+
+    def _generate_paged(self, input_ids, max_new_tokens, temperature, top_k,
+                        top_p, eos_id, seed):
+        ragged = not isinstance(input_ids, torch.Tensor)
+        prompts, lens, cache, logits = self._prefill_paged(input_ids,
+                                                           max_new_tokens)
+        B = len(prompts)
+        gen = torch.Generator(device="cpu").manual_seed(seed)
         new = []
         alive = torch.ones(B, dtype=torch.bool)
         for _ in range(max_new_tokens):

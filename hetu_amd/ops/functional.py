@@ -1371,7 +1371,7 @@ def _prefill_paged_torch(q, k_pool, v_pool, block_table, cu_q, kv_len,
 
 
 def flash_attn_prefill_paged(q, k_pool, v_pool, block_table, cu_q, kv_len,
-                             scale=None, max_q=None, impl=None):
+                             scale=None, max_q=None, impl=None, num_splits=0):
     """Causal attention of a packed, ragged batch of query chunks over a paged
     KV cache, each chunk at the END of its sequence's cached keys.
 
@@ -1398,10 +1398,23 @@ def flash_attn_prefill_paged(q, k_pool, v_pool, block_table, cu_q, kv_len,
     attention capture into one graph; an error on anything else, never a
     fallback); "torch" = the definition in fp32 torch ops, one sequence at a
     time (it reads cu_q and kv_len on the host); None = the kernel for every
-    eligible input, else torch (and with HETU_AMD_TORCH_FALLBACK=fa)."""
-    if impl not in (None, "torch", "hip"):
+    eligible input, else torch (and with HETU_AMD_TORCH_FALLBACK=fa);
+    "split" = ops/hip/attention_verify_paged.hip, the split-KV kernel for
+    chunks of a few tokens behind a long context (speculative verification):
+    the keys of a sequence are read once for all its rows and spread over
+    num_splits blocks per KV head (0 = from the shapes and the CU count, at
+    most 64).  Same inputs as "hip", same contract, also an error on anything
+    else; it is explicit only, None never picks it, and it does not look at
+    HETU_AMD_TORCH_FALLBACK (whoever asks for a kernel by name gets it).
+    There max_q also picks the row tile: rows past it are still computed.
+    num_splits must be 0 with any other impl."""
+    if impl not in (None, "torch", "hip", "split"):
         raise ValueError("flash_attn_prefill_paged: impl must be None, "
-                         f"'torch' or 'hip', got {impl!r}")
+                         f"'torch', 'hip' or 'split', got {impl!r}")
+    if impl != "split" and num_splits != 0:
+        raise ValueError("flash_attn_prefill_paged: num_splits is "
+                         f"{num_splits} with impl={impl!r}; only "
+                         "impl='split' takes it")
     if q.dim() != 3 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape \
             or k_pool.shape[3] != q.shape[2] or k_pool.shape[1] < 1 \
             or q.shape[1] % k_pool.shape[1] \
@@ -1423,8 +1436,15 @@ def flash_attn_prefill_paged(q, k_pool, v_pool, block_table, cu_q, kv_len,
         scale = 1.0 / math.sqrt(q.shape[-1])
     why = _prefill_paged_ineligible(q, k_pool, v_pool, block_table, cu_q,
                                     kv_len)
-    if impl == "hip" and why is not None:
-        raise ValueError(f"flash_attn_prefill_paged(impl='hip'): {why}")
+    if impl == "split" and why is None and not 0 <= num_splits <= 64:
+        why = f"num_splits is {num_splits}, not in [0, 64]"
+    if impl in ("hip", "split") and why is not None:
+        raise ValueError(f"flash_attn_prefill_paged(impl={impl!r}): {why}")
+    if impl == "split":
+        out, lse = ext().flash_attn_verify_paged(
+            q, k_pool, v_pool, block_table, cu_q, kv_len, float(scale),
+            int(q.shape[0] if max_q is None else max_q), int(num_splits))
+        return out, lse
     if impl == "torch" or (impl is None
                            and (why is not None or "fa" in _TORCH_FB)):
         return _prefill_paged_torch(q, k_pool, v_pool, block_table, cu_q,

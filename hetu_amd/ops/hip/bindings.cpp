@@ -189,6 +189,11 @@ std::vector<torch::Tensor> flash_attn_prefill_paged(
     torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
     torch::Tensor block_table, torch::Tensor cu_q, torch::Tensor kv_len,
     double scale, int64_t max_q);
+// attention_verify_paged.hip
+std::vector<torch::Tensor> flash_attn_verify_paged(
+    torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+    torch::Tensor block_table, torch::Tensor cu_q, torch::Tensor kv_len,
+    double scale, int64_t max_q, int64_t num_splits);
 // attention_decode_fp8.hip
 int64_t decode_attn_fp8_tile();
 std::vector<torch::Tensor> flash_attn_decode_fp8(
@@ -311,4 +316,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
         py::arg("cu_q"), py::arg("kv_len"), py::arg("scale"),
         py::arg("max_q"));
+  m.def("flash_attn_verify_paged", &flash_attn_verify_paged, py::arg("q"),
+        py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+        py::arg("cu_q"), py::arg("kv_len"), py::arg("scale"),
+        py::arg("max_q"), py::arg("num_splits") = 0);
 }

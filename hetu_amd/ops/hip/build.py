@@ -38,6 +38,7 @@ SOURCES = [
     "attention_decode_fp8.hip",
     "attention_decode_paged.hip",
     "attention_prefill_paged.hip",
+    "attention_verify_paged.hip",
     "kv_cache_fp8.hip",
     "kv_cache_paged.hip",
     "quant.hip",
@@ -59,6 +60,7 @@ EXTRA_FLAGS = {
     "kv_cache_fp8.hip": _NO_PK_F32,
     "kv_cache_paged.hip": _NO_PK_F32,
     "attention_prefill_paged.hip": _NO_PK_F32,
+    "attention_verify_paged.hip": _NO_PK_F32,
     # attention_decode_paged.hip instantiates attention_decode.hip's kernel
     # (attention_decode_valu.h) and has to stay bit-identical to it, so it
     # takes that file's flags: which multiplies and adds become fmas follows
