@@ -16,8 +16,9 @@ kernels as training via ops.functional.
 With kv_layout="paged" the cache is a page pool behind a block table and
 generate() takes ragged prompts.  prefill="sequence" prefills them one at a
 time through the dense path; prefill="packed" runs them as one packed forward
-over the pages (F.flash_attn_prefill_paged), optionally in rounds of
-prefill_chunk tokens that attend the context already cached.  kv_dtype="fp8"
+over the pages (F.flash_attn_prefill_paged: on the GPU, for bf16 and head dim
+64 or 128, the HIP prefill kernel), optionally in rounds of prefill_chunk
+tokens that attend the context already cached.  kv_dtype="fp8"
 makes the pages e4m3 codes with one fp32 scale per cached row (prefill=
 "sequence" only: the prefill attends the bf16 rows it just computed).
 
@@ -185,6 +186,12 @@ class PagedKVCache:
 
 
 class LlamaGenerator:
+    """KV-cached Llama generation.  With kv_layout="paged", prefill="packed"
+    and bf16 weights on the GPU every attention call at head dim 64 or 128 is
+    a HIP kernel: the packed append, the prefill kernel over the pages, the
+    split-KV verification kernel of generate(speculative=k) and the paged
+    decode kernels."""
+
     def __init__(self, cfg: LlamaConfig, state: Dict[str, torch.Tensor],
                  device: Optional[torch.device] = None,
                  dtype: torch.dtype = torch.float32,

@@ -1308,8 +1308,8 @@ def _prefill_paged_ineligible(q, k_pool, v_pool, block_table, cu_q,
             return f"{name} is not on the GPU"
         if t.dtype != torch.bfloat16:
             return f"{name} is {t.dtype}, not bf16"
-    if q.shape[-1] != 128:
-        return f"the head dim of q is {q.shape[-1]}, not 128"
+    if q.shape[-1] not in (64, 128):
+        return f"the head dim of q is {q.shape[-1]}, not 64 or 128"
     for name, t in ts:
         if t.stride(-1) != 1:
             return f"{name} has a non-unit last stride"
@@ -1393,10 +1393,10 @@ def flash_attn_prefill_paged(q, k_pool, v_pool, block_table, cu_q, kv_len,
     grid (as max_seqlen does for flash_attn_varlen_bwd): rows of a longer
     chunk past it are not computed.
 
-    impl: "hip" = ops/hip/attention_prefill_paged.hip (bf16, D = 128, GPU, any
-    H / Hkv; one launch, lengths and table read on the device, so append +
-    attention capture into one graph; an error on anything else, never a
-    fallback); "torch" = the definition in fp32 torch ops, one sequence at a
+    impl: "hip" = ops/hip/attention_prefill_paged.hip (bf16, D = 64 or 128,
+    GPU, any H / Hkv; one launch, lengths and table read on the device, so
+    append + attention capture into one graph; an error on anything else,
+    never a fallback); "torch" = the definition in fp32 torch ops, one sequence at a
     time (it reads cu_q and kv_len on the host); None = the kernel for every
     eligible input, else torch (and with HETU_AMD_TORCH_FALLBACK=fa);
     "split" = ops/hip/attention_verify_paged.hip, the split-KV kernel for

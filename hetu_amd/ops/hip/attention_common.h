@@ -230,6 +230,99 @@ DEV void fa_store_row_bf16(const f32x16 (&acc)[4], float mul, bf16* row,
                      acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
 }
 
+// ---- D-parametrised siblings (D = 64 or 128) ------------------------------
+// For the kernels that serve both head dims (attention_prefill_paged.hip).
+// At D = 128 each one is the function above; what follows describes D = 64.
+//
+// Row-major K image at D = 64: [rows][128 B].  LDS has 64 banks of 4 B, a
+// 256-B bank line, so two rows share a line: row r covers bytes 128 (r & 1)
+// .. + 127 of line r >> 1.  A ds_read_b128 is served 16 lanes at a time, and
+// in S^T = mfma(K, Q) the 16 lanes of such a group read the SAME 16-B slot s
+// (8 per row) of 16 consecutive rows r0 .. r0 + 15, r0 a multiple of 16.
+// Unswizzled those are 2 distinct 16-B columns of the line, an 8-way conflict.
+// With slot' = s ^ ((r >> 1) & 7) the 8 row pairs of the group carry 8
+// distinct values of (r >> 1) & 7, hence 8 distinct slots, and the two rows
+// of a pair sit in different halves of the line: 16 distinct 16-B columns,
+// every bank exactly once.  This is derived from the bank arithmetic above,
+// not measured with counters.
+template <int D>
+DEV int fa_swz_rm_d(int row, int byte_in_row) {
+  if constexpr (D == 128) return fa_swz_rm(row, byte_in_row);
+  else return row * 128 + (byte_in_row ^ (((row >> 1) & 7) << 4));
+}
+
+// inverse for staging: the source element column whose 16 B land at linear
+// image byte `pos` (row = pos / (2 D)).  A 1 KiB DMA instruction is 4 rows at
+// D = 128 and 8 rows at D = 64.
+template <int D>
+DEV int fa_rm_src_col_d(int pos) {
+  if constexpr (D == 128) return fa_rm_src_col(pos);
+  else return ((pos & 127) ^ (((pos >> 8) & 7) << 4)) >> 1;
+}
+
+// V image: [key group][d subtile] subtiles of [32 keys][16 d] bf16 (1 KiB
+// each), D / 16 d-subtiles per 32-key group.  At D = 64 a 16 KiB image holds
+// four groups (128 keys) of four subtiles.
+template <int D>
+DEV int fa_voff_d(int key, int d) {
+  return ((key >> 5) * (D / 16) + (d >> 4)) * 1024 + (key & 31) * 32 +
+         (d & 15) * 2;
+}
+
+// D = 64: the V^T fragments d[s][dt] (row d = 32 dt + iq, k = keys
+// 32 grp + 16 s + 8 hi ..) of BOTH 16-key slots of the 32-key group grp.  In
+// fa_voff_d<64> a slot is +512 B, key + 4 is +128 B and a 32-d tile is
+// +2048 B, all inside the group's 4 KiB: 8 transposed reads from ONE address
+// under a single lgkmcnt wait, as in fa_tr_v4.
+DEV void fa_tr_v2x2(bf16x8 (&d)[2][2], const char* v_img, int grp, int lane) {
+  const int hi = lane >> 5;
+  const int keyb = 32 * grp + 8 * hi + ((lane >> 2) & 3);
+  const int dbase0 = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const unsigned a1 = fa_lds_addr(v_img + fa_voff_d<64>(keyb, dbase0));
+  u32x2 r1[4], r2[4];
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %8\n\t"
+      "ds_read_b64_tr_b16 %1, %8 offset:128\n\t"
+      "ds_read_b64_tr_b16 %2, %8 offset:2048\n\t"
+      "ds_read_b64_tr_b16 %3, %8 offset:2176\n\t"
+      "ds_read_b64_tr_b16 %4, %8 offset:512\n\t"
+      "ds_read_b64_tr_b16 %5, %8 offset:640\n\t"
+      "ds_read_b64_tr_b16 %6, %8 offset:2560\n\t"
+      "ds_read_b64_tr_b16 %7, %8 offset:2688\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(r1[0]), "=&v"(r2[0]), "=&v"(r1[1]), "=&v"(r2[1]),
+        "=&v"(r1[2]), "=&v"(r2[2]), "=&v"(r1[3]), "=&v"(r2[3])
+      : "v"(a1));
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+      d[s][dt] = fa_join(r1[2 * s + dt], r2[2 * s + dt]);
+}
+
+// A lane's row as D / 16 MFMA fragments: frags[kk] = row[16 kk + 8 hi .. + 8)
+template <int D>
+DEV void fa_load_row_frags_d(bf16x8 (&frags)[D / 16], const bf16* row,
+                             int hi) {
+#pragma unroll
+  for (int kk = 0; kk < D / 16; ++kk)
+    frags[kk] = *reinterpret_cast<const bf16x8*>(row + kk * 16 + hi * 8);
+}
+
+// O epilogue over D / 32 accumulator tiles (fa_store_row_bf16's layout)
+template <int D>
+DEV void fa_store_row_bf16_d(const f32x16 (&acc)[D / 32], float mul,
+                             bf16* row, int hi) {
+#pragma unroll
+  for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      fa_store4_bf16(row + 32 * dt + 8 * g + 4 * hi,
+                     acc[dt][4 * g + 0] * mul, acc[dt][4 * g + 1] * mul,
+                     acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
+}
+
 // dkv: stage the wave's own 32 V rows (8 KiB) into its row-major image;
 // rows past Skv clamp to the last valid one
 DEV void fa_stage_wave_v(const bf16* Vb, int64_t row_stride, int key0,

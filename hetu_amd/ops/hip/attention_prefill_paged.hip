@@ -2,10 +2,10 @@
 // bf16 KV cache, for gfx950: the prefill (and chunked prefill) kernel behind
 // the block-table decode kernels.
 //
-//   q [T, H, D = 128] packed over sequences (element strides: a view into a
-//   fused qkv output is read in place), k_pool / v_pool [P, Hkv, PS, D] (with
-//   their strides), block_table int32 [B, MP], cu_q int32 [B + 1] and kv_len
-//   int32 [B] on the device -> out [T, H, D] bf16, lse [H, T] fp32
+//   q [T, H, D = 64 or 128] packed over sequences (element strides: a view
+//   into a fused qkv output is read in place), k_pool / v_pool [P, Hkv, PS, D]
+//   (with their strides), block_table int32 [B, MP], cu_q int32 [B + 1] and
+//   kv_len int32 [B] on the device -> out [T, H, D] bf16, lse [H, T] fp32
 //
 // n_b = cu_q[b + 1] - cu_q[b], kv_b = clamp(kv_len[b], 0, MP * PS): the chunk
 // sits at the END of its sequence's cached keys, so row i of sequence b stands
@@ -41,6 +41,22 @@
 //    fp32 (q is NOT pre-scaled in bf16: that rounding moves lse by more than
 //    the bound allows on a sharp row) and exp is the bare v_exp_f32.
 //
+// D = 64 keeps the 8 x 32 M-rows, the 16 KiB images, the ring and the counted
+// wait, and changes what a byte of them means (the text above is D = 128):
+//  * A K row is 128 B, so an image is a 128-KEY tile: four 32-key blocks of
+//    S^T (p[4][16]) with 4 k-steps each, and two 32-d accumulator tiles of O.
+//    The K image takes fa_swz_rm_d<64> (two rows per bank line, derived in
+//    attention_common.h), the V image is [key group][d subtile] with four
+//    d-subtiles per group.
+//  * A 1 KiB DMA instruction is 8 consecutive K rows or one [32 key][16 d] V
+//    subtile.  Wave w stages K rows 16 w .. 16 w + 15 and V subtiles 2 w and
+//    2 w + 1: all in the 32-key group w >> 1, so it is still one page and one
+//    scalar id per wave and tile.  Every wave consumes all four groups and
+//    reads four ids per tile; the unloaded-group bits are four per tile.
+//  * P.V takes a group at a time: both 16-key slots' V^T fragments come from
+//    one fa_tr_v2x2 (8 transposed reads, one wait) and feed 4 MFMAs; the two
+//    k-steps of an unloaded group are skipped together.
+//
 // Grid (B + 1) * Hkv * (G / GP) by ceil(max_q * GP / 256): sequence and head
 // on blockIdx.x (docs/KERNELS.md, XCD grid order).  It depends on shapes and
 // max_q only; blocks past a sequence's chunk return before any load or
@@ -55,7 +71,6 @@
 namespace {
 
 constexpr int PF_BM = 256;             // M-rows per block (8 waves x 32)
-constexpr int PF_BN = 64;              // key tile
 constexpr int PF_NGLDS = FA_KV_IMG / (FA_THREADS * 16);   // per lane and image
 constexpr int PF_NBUF = FA_RING;
 
@@ -63,7 +78,7 @@ struct PfArgs {
   const bf16* q;
   const bf16* k;
   const bf16* v;
-  bf16* out;                  // [T, H, 128]
+  bf16* out;                  // [T, H, D]
   float* lse;                 // [H, T]
   const int* table;           // [B, MP]
   const int* cu_q;            // [B + 1]
@@ -76,15 +91,30 @@ struct PfArgs {
   bool mask_all;
 };
 
-// 2 bits: the 32-key groups of a tile whose page id is outside [0, P)
-DEV int pf_bad_bits(int id0, int id1, int P) {
-  return ((unsigned)id0 >= (unsigned)P ? 1 : 0) |
-         ((unsigned)id1 >= (unsigned)P ? 2 : 0);
+// one bit per 32-key group of a tile (2 at D = 128, 4 at D = 64) whose page id
+// is outside [0, P)
+template <int NG>
+DEV int pf_bad_bits(const int (&id)[NG], int P) {
+  int bad = 0;
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+    bad |= (unsigned)id[g] >= (unsigned)P ? 1 << g : 0;
+  return bad;
 }
 
-template <int GP>
+template <int GP, int D>
 __global__ __launch_bounds__(FA_THREADS, 1)
 void fa_prefill_paged_kernel(PfArgs a) {
+  static_assert(D == 64 || D == 128, "head dim");
+  constexpr int PF_BN = FA_KV_IMG / (2 * D);   // key tile: 64 (D = 128) / 128
+  constexpr int NG = PF_BN / 32;       // 32-key groups = S^T blocks of a tile
+  constexpr int NKK = D / 16;          // k-steps of S^T
+  constexpr int NDT = D / 32;          // 32-d accumulator tiles of O
+  constexpr int GRP_SH = D == 128 ? 2 : 1;     // log2 of waves staging a group
+  constexpr int KROW_SH = D == 128 ? 8 : 7;    // log2 of a K row's bytes
+  constexpr int VSUB_SH = D == 128 ? 3 : 2;    // log2 of d-subtiles a group
+  constexpr int ROW_CH = D / 8;        // 16-B chunks of an output row
+  constexpr int ALL_BAD = (1 << NG) - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int i) -> char* { return smem + i * FA_KV_IMG; };
   auto v_lds = [&](int i) -> char* {
@@ -102,16 +132,16 @@ void fa_prefill_paged_kernel(PfArgs a) {
   if (b == a.B) {
     // rows past cu_q[B]: 16 B of zeros per thread and step, no loads
     const int t0 = min(max(a.cu_q[a.B], 0), a.T);
-    const long long total = (long long)(a.T - t0) * (GP * 16);
+    const long long total = (long long)(a.T - t0) * (GP * ROW_CH);
     ushort8 z;
 #pragma unroll
     for (int j = 0; j < 8; ++j) z.v[j] = 0;
     for (long long i = (long long)blockIdx.y * FA_THREADS + tid; i < total;
          i += (long long)gridDim.y * FA_THREADS) {
-      const int t = t0 + (int)(i / (GP * 16));
-      const int h = head0 + (int)(i % (GP * 16)) / 16;
-      const int ch = (int)(i % 16);
-      *reinterpret_cast<ushort8*>(a.out + ((int64_t)t * a.H + h) * 128 +
+      const int t = t0 + (int)(i / (GP * ROW_CH));
+      const int h = head0 + (int)(i % (GP * ROW_CH)) / ROW_CH;
+      const int ch = (int)(i % ROW_CH);
+      *reinterpret_cast<ushort8*>(a.out + ((int64_t)t * a.H + h) * D +
                                   ch * 8) = z;
       if (ch == 0) a.lse[(int64_t)h * a.T + t] = -INFINITY;
     }
@@ -138,7 +168,7 @@ void fa_prefill_paged_kernel(PfArgs a) {
 
   // wave-uniform: the wave's tokens, the block's key range
   const int wu = __builtin_amdgcn_readfirstlane(wid);
-  const int grp = wu >> 2;             // the 32-key group this wave stages
+  const int grp = wu >> GRP_SH;        // the 32-key group this wave stages
   const int wtok0 = (blockIdx.y * PF_BM + wu * 32) / GP;
   const int wtok1 = (blockIdx.y * PF_BM + wu * 32 + 31) / GP;
   const bool w_any = wtok0 < n_b;
@@ -150,18 +180,31 @@ void fa_prefill_paged_kernel(PfArgs a) {
   const int klast = kend - 1;          // every key is clamped to it
 
   // Q -> registers, unscaled (the scale meets the scores in fp32)
-  bf16x8 qreg[8];
-  fa_load_row_frags(qreg,
-                    a.q + (int64_t)(row0 + min(tok, n_b - 1)) * a.q_ts +
-                        (int64_t)head * a.q_hs, hi);
+  bf16x8 qreg[NKK];
+  fa_load_row_frags_d<D>(qreg,
+                         a.q + (int64_t)(row0 + min(tok, n_b - 1)) * a.q_ts +
+                             (int64_t)head * a.q_hs, hi);
 
   typedef const __attribute__((address_space(4))) int* const_int_p;
   const const_int_p trow = (const_int_p)(a.table + (int64_t)b * a.MP);
-  // the ids of both 32-key groups of the tile at k0 (klast >= 0 here)
-  auto ids_of = [&](int k0, int& id0, int& id1) {
-    id0 = __builtin_amdgcn_readfirstlane(trow[min(k0, klast) >> a.ps_shift]);
-    id1 = __builtin_amdgcn_readfirstlane(
-        trow[min(k0 + 32, klast) >> a.ps_shift]);
+  // the ids of the 32-key groups of the tile at k0 (klast >= 0 here)
+  auto ids_of = [&](int k0, int (&id)[NG]) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      id[g] = __builtin_amdgcn_readfirstlane(
+          trow[min(k0 + 32 * g, klast) >> a.ps_shift]);
+  };
+  // the id of the wave's own group, by scalar selection (two levels on the
+  // bits of grp; the readfirstlane keeps the four-way form in an SGPR, which
+  // dec_page_landed requires)
+  auto own_id = [&](const int (&id)[NG]) {
+    if constexpr (NG == 2) {
+      return grp ? id[1] : id[0];
+    } else {
+      const int lo = (grp & 1) ? id[1] : id[0];
+      const int hi2 = (grp & 1) ? id[3] : id[2];
+      return __builtin_amdgcn_readfirstlane((grp & 2) ? hi2 : lo);
+    }
   };
 
   const bf16* kb = a.k + (int64_t)hkv * a.k_hs;
@@ -176,37 +219,37 @@ void fa_prefill_paged_kernel(PfArgs a) {
 #pragma unroll
     for (int i = 0; i < PF_NGLDS; ++i) {
       const int pos = (wid * PF_NGLDS + i) * 1024 + lane * 16;
-      const int krow = min(k0 + (pos >> 8), klast) & rmask;
-      fa_glds16(kp + (int64_t)krow * a.k_rs + fa_rm_src_col(pos),
+      const int krow = min(k0 + (pos >> KROW_SH), klast) & rmask;
+      fa_glds16(kp + (int64_t)krow * a.k_rs + fa_rm_src_col_d<D>(pos),
                 k_lds(buf) + pos);
       const int st = pos >> 10;
-      const int vkey = (st >> 3) * 32 + ((pos >> 5) & 31);
-      const int vd = (st & 7) * 16 + ((pos >> 4) & 1) * 8;
+      const int vkey = (st >> VSUB_SH) * 32 + ((pos >> 5) & 31);
+      const int vd = (st & (D / 16 - 1)) * 16 + ((pos >> 4) & 1) * 8;
       const int vrow = min(k0 + vkey, klast) & rmask;
       fa_glds16(vp + (int64_t)vrow * a.v_rs + vd, v_lds(buf) + pos);
     }
   };
 
-  f32x16 o_acc[4];
+  f32x16 o_acc[NDT];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
+  for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) o_acc[dt][i] = 0.f;
   float m_i = -INFINITY, l_i = 0.f;    // base-2 running max and sum
 
   // prologue: tiles 0 and 1 in flight, the ids of tile 2 requested.
   // bad_c / bad_n: the unloaded groups of tiles t and t + 1.
-  int bad_c = 0, bad_n = 0, id0_n = 0, id1_n = 0;
+  int bad_c = 0, bad_n = 0, id_n[NG] = {};
   if (n_tiles > 0) {
-    int id0, id1;
-    ids_of(0, id0, id1);
-    bad_c = pf_bad_bits(id0, id1, a.P);
-    if (!((bad_c >> grp) & 1)) stage(0, 0, grp ? id1 : id0);
-    ids_of(PF_BN, id0, id1);
-    bad_n = pf_bad_bits(id0, id1, a.P);
+    int id[NG];
+    ids_of(0, id);
+    bad_c = pf_bad_bits(id, a.P);
+    if (!((bad_c >> grp) & 1)) stage(0, 0, own_id(id));
+    ids_of(PF_BN, id);
+    bad_n = pf_bad_bits(id, a.P);
     if (n_tiles > 1 && !((bad_n >> grp) & 1))
-      stage(PF_BN, 1, grp ? id1 : id0);
-    ids_of(2 * PF_BN, id0_n, id1_n);
+      stage(PF_BN, 1, own_id(id));
+    ids_of(2 * PF_BN, id_n);
   }
 
   for (int t = 0; t < n_tiles; ++t) {
@@ -216,29 +259,29 @@ void fa_prefill_paged_kernel(PfArgs a) {
     // nothing for tile t + 1
     fa_wait_tile<2 * PF_NGLDS>(t + 1 >= n_tiles || ((bad_n >> grp) & 1));
     __builtin_amdgcn_s_barrier();
-    const int bad_nn = pf_bad_bits(id0_n, id1_n, a.P);
+    const int bad_nn = pf_bad_bits(id_n, a.P);
     {
-      int page = grp ? id1_n : id0_n;
+      int page = own_id(id_n);
       int key_nn = k0 + 3 * PF_BN;
       dec_page_landed(page, key_nn);   // old ids first, then the new request
       if (t + 2 < n_tiles && !((bad_nn >> grp) & 1))
         stage(k0 + 2 * PF_BN, (t + 2) % PF_NBUF, page);
-      ids_of(key_nn, id0_n, id1_n);
+      ids_of(key_nn, id_n);
     }
 
     // any row of the wave with an unmasked key in a loaded group?
-    const bool active = w_any && k0 <= w_pmax && bad_c != 3;
+    const bool active = w_any && k0 <= w_pmax && bad_c != ALL_BAD;
     if (active) {
-      float p[2][16];
+      float p[NG][16];
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
+      for (int ct = 0; ct < NG; ++ct) {
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
+        for (int kk = 0; kk < NKK; ++kk) {
           bf16x8 kf = *reinterpret_cast<const bf16x8*>(
-              k_lds(cur) + fa_swz_rm(32 * ct + iq, kk * 32 + hi * 16));
+              k_lds(cur) + fa_swz_rm_d<D>(32 * ct + iq, kk * 32 + hi * 16));
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qreg[kk], acc,
                                                         0, 0, 0);
         }
@@ -251,16 +294,17 @@ void fa_prefill_paged_kernel(PfArgs a) {
       auto softmax = [&](auto mask_c) -> float {
         constexpr bool MASK = decltype(mask_c)::value;
         float pmax = -INFINITY;
-        int bound[2] = {0, 0};
+        int bound[NG] = {};
         if constexpr (MASK) {
           // one compare per element: the lane's last key relative to its
           // first register's key; -1 masks a padded row or an unloaded group
           const int bl = valid ? my_p - (k0 + 4 * hi) : -1;
-          bound[0] = (bad_c & 1) ? -1 : bl;
-          bound[1] = (bad_c & 2) ? -1 : bl;
+#pragma unroll
+          for (int ct = 0; ct < NG; ++ct)
+            bound[ct] = (bad_c & (1 << ct)) ? -1 : bl;
         }
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
+        for (int ct = 0; ct < NG; ++ct)
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             if constexpr (MASK)
@@ -274,7 +318,7 @@ void fa_prefill_paged_kernel(PfArgs a) {
         m_i = mn;
         float psum = 0.f;
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
+        for (int ct = 0; ct < NG; ++ct)
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             float pv;
@@ -293,25 +337,44 @@ void fa_prefill_paged_kernel(PfArgs a) {
       // wave-uniform: the tile crosses the causal diagonal of the wave's
       // first token or the key tail, the wave holds padded rows, or a group
       // of the tile is not loaded
-      const bool boundary = a.mask_all || k0 + 63 > w_pmin ||
-                            k0 + 63 >= kv_b || w_pad || bad_c != 0;
+      const bool boundary = a.mask_all || k0 + (PF_BN - 1) > w_pmin ||
+                            k0 + (PF_BN - 1) >= kv_b || w_pad || bad_c != 0;
       const float alpha = boundary ? softmax(std::true_type{})
                                    : softmax(std::false_type{});
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
+      for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) o_acc[dt][i] *= alpha;
 
+      if constexpr (D == 128) {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        if ((bad_c >> (ks >> 1)) & 1) continue;   // stale V image: skip
-        bf16x8 pfrag = fa_pack_frag(p[ks >> 1], (ks & 1) * 8);
-        bf16x8 vf[4];
-        fa_tr_v4(vf, v_lds(cur), ks, lane);
+        for (int ks = 0; ks < 4; ++ks) {
+          if ((bad_c >> (ks >> 1)) & 1) continue;   // stale V image: skip
+          bf16x8 pfrag = fa_pack_frag(p[ks >> 1], (ks & 1) * 8);
+          bf16x8 vf[4];
+          fa_tr_v4(vf, v_lds(cur), ks, lane);
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              vf[dt], pfrag, o_acc[dt], 0, 0, 0);
+          for (int dt = 0; dt < 4; ++dt)
+            o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                vf[dt], pfrag, o_acc[dt], 0, 0, 0);
+        }
+      } else {
+        // a 32-key group at a time: its two k-steps share one V read block
+        // and are skipped together where the group was not loaded
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          if ((bad_c >> g) & 1) continue;           // stale V image: skip
+          bf16x8 vf[2][2];
+          fa_tr_v2x2(vf, v_lds(cur), g, lane);
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            bf16x8 pfrag = fa_pack_frag(p[g], s * 8);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+              o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  vf[s][dt], pfrag, o_acc[dt], 0, 0, 0);
+          }
+        }
       }
     }
     bad_c = bad_n;
@@ -320,8 +383,8 @@ void fa_prefill_paged_kernel(PfArgs a) {
 
   if (valid) {
     const float inv = (l_i > 0.f) ? 1.f / l_i : 0.f;
-    fa_store_row_bf16(o_acc, inv,
-                      a.out + ((int64_t)(row0 + tok) * a.H + head) * 128, hi);
+    fa_store_row_bf16_d<D>(
+        o_acc, inv, a.out + ((int64_t)(row0 + tok) * a.H + head) * D, hi);
     if (hi == 0)
       a.lse[(int64_t)head * a.T + row0 + tok] =
           (l_i > 0.f) ? (m_i + __log2f(l_i)) * 0.6931471805599453f
@@ -362,8 +425,8 @@ std::vector<torch::Tensor> flash_attn_prefill_paged(
   const int64_t T = q.size(0), H = q.size(1), D = q.size(2);
   const int64_t P = k_pool.size(0), Hkv = k_pool.size(1);
   const int64_t PS = k_pool.size(2);
-  TORCH_CHECK(D == 128 && k_pool.size(3) == D, fn, "D must be 128, got ", D,
-              " and ", k_pool.size(3));
+  TORCH_CHECK((D == 64 || D == 128) && k_pool.size(3) == D, fn,
+              "D must be 64 or 128, got ", D, " and ", k_pool.size(3));
   TORCH_CHECK(Hkv >= 1 && H % Hkv == 0, fn, "H (", H,
               ") is not a multiple of Hkv (", Hkv, ")");
   TORCH_CHECK(PS == 32 || PS == 64 || PS == 128 || PS == 256, fn,
@@ -384,8 +447,9 @@ std::vector<torch::Tensor> flash_attn_prefill_paged(
               kv_len.size(0) == B, fn, "need cu_q [B + 1] and kv_len [B] "
               "with B = ", B, " rows of block_table");
   const int64_t lim = (int64_t)1 << 31;
-  TORCH_CHECK(T < lim && H < lim && P < lim && MP < lim / PS && B < lim, fn,
-              "T, H, B, P or MP * PS too large for int");
+  // the id prefetch forms keys up to four 128-key tiles past the first
+  TORCH_CHECK(T < lim && H < lim && P < lim && MP * PS < lim - 512 &&
+              B < lim, fn, "T, H, B, P or MP * PS too large for int");
 
   auto out = torch::empty({T, H, D}, q.options());
   auto lse = torch::empty({H, T}, q.options().dtype(at::kFloat));
@@ -420,13 +484,19 @@ std::vector<torch::Tensor> flash_attn_prefill_paged(
 
   const dim3 grid((unsigned)gx, (unsigned)gy);
   auto stream = hetu_current_stream();
-#define PF_LAUNCH(GG)                                                      \
-  hipLaunchKernelGGL((fa_prefill_paged_kernel<GG>), grid,                  \
+#define PF_LAUNCH(GG, DD)                                                  \
+  hipLaunchKernelGGL((fa_prefill_paged_kernel<GG, DD>), grid,              \
                      dim3(FA_THREADS), FA_FWD_LDS, stream, a)
-  if (gp == 8) PF_LAUNCH(8);
-  else if (gp == 4) PF_LAUNCH(4);
-  else if (gp == 2) PF_LAUNCH(2);
-  else PF_LAUNCH(1);
+#define PF_LAUNCH_D(DD)                                                    \
+  do {                                                                     \
+    if (gp == 8) PF_LAUNCH(8, DD);                                         \
+    else if (gp == 4) PF_LAUNCH(4, DD);                                    \
+    else if (gp == 2) PF_LAUNCH(2, DD);                                    \
+    else PF_LAUNCH(1, DD);                                                 \
+  } while (0)
+  if (D == 128) PF_LAUNCH_D(128);
+  else PF_LAUNCH_D(64);
+#undef PF_LAUNCH_D
 #undef PF_LAUNCH
   HIP_CHECK(hipGetLastError());
   return {out, lse};

@@ -5,9 +5,9 @@
 // (attention_prefill_paged.hip), the plan is the MFMA decode kernel's
 // (attention_decode_mfma.hip).
 //
-//   q [T, H, D = 128] packed over sequences (element strides), k_pool / v_pool
-//   [P, Hkv, PS, D] (with their strides), block_table int32 [B, MP], cu_q
-//   int32 [B + 1] and kv_len int32 [B] on the device
+//   q [T, H, D = 64 or 128] packed over sequences (element strides), k_pool /
+//   v_pool [P, Hkv, PS, D] (with their strides), block_table int32 [B, MP],
+//   cu_q int32 [B + 1] and kv_len int32 [B] on the device
 //   -> out [T, H, D] bf16, lse [H, T] fp32
 //
 // n_b = cu_q[b + 1] - cu_q[b], kv_b = clamp(kv_len[b], 0, MP * PS); row i of
@@ -65,7 +65,6 @@
 
 namespace {
 
-constexpr int VF_D = 128;
 constexpr float VF_LN2 = 0.6931471805599453f;
 
 // DecPagedArgs with q_bs the token stride of q, out [T, H, D], lse [H, T] and
@@ -76,21 +75,22 @@ struct VfArgs : DecPagedArgs {
   float scale_log2;   // scale * log2(e)
 };
 
-DEV void vf_zero_row(bf16* dst) {      // 16 B of a [.., 128] bf16 row
+DEV void vf_zero_row(bf16* dst) {      // 16 B of a [.., D] bf16 row
   ushort8 z;
 #pragma unroll
   for (int j = 0; j < 8; ++j) z.v[j] = 0;
   *reinterpret_cast<ushort8*>(dst) = z;
 }
 
-// one block per CU with two or four row tiles (512 registers a lane), two with
-// one: what compiles without scratch (profiles/r15_verify_paged.md)
-template <int MT>
-__global__ __launch_bounds__(DM_THREADS, MT >= 2 ? 1 : 2)
+// D = 128: one block per CU with two or four row tiles (512 registers a lane),
+// two with one: what compiles without scratch (profiles/r15_verify_paged.md).
+// D = 64 halves q, the K fragments and the accumulators and fits two blocks
+// per CU at every MT (profiles/r16_paged_d64.md).
+template <int MT, int D>
+__global__ __launch_bounds__(DM_THREADS, (D == 128 && MT >= 2) ? 1 : 2)
 void fa_verify_paged_kernel(VfArgs a) {
-  constexpr int D = VF_D;
   constexpr int RB = 2 * D;
-  constexpr int IMG = DM_WKEYS * RB;           // 8 KiB
+  constexpr int IMG = DM_WKEYS * RB;           // 8 KiB (D = 128) / 4 KiB
   constexpr int NV = IMG / 1024;               // DMA instructions per tile
   constexpr int KS = D / 32;
   constexpr int NDB = D / 16;
@@ -381,13 +381,13 @@ void fa_verify_paged_kernel(VfArgs a) {
 // out[t, h] = sum_s exp(lse_s - lse) * o_s over the non-empty splits, in split
 // order, lse [H, T]; rows at or past cu_q[B] are 0 / -inf without a read of
 // the workspace (no block wrote it).  One block per (t, h), one thread per dim.
+template <int D>
 __global__ void fa_verify_merge_kernel(const float* __restrict__ ws_o,
                                        const float* __restrict__ ws_lse,
                                        bf16* __restrict__ out,
                                        float* __restrict__ lse,
                                        const int* __restrict__ cu_q, int B,
                                        int T, int H, int ns) {
-  constexpr int D = VF_D;
   const int64_t row = blockIdx.x;
   const int t = (int)(row / H), h = (int)(row % H);
   const int d = threadIdx.x;
@@ -444,8 +444,8 @@ std::vector<torch::Tensor> flash_attn_verify_paged(
   const int64_t T = q.size(0), H = q.size(1), D = q.size(2);
   const int64_t P = k_pool.size(0), Hkv = k_pool.size(1);
   const int64_t PS = k_pool.size(2);
-  TORCH_CHECK(D == VF_D && k_pool.size(3) == D, fn, "D must be 128, got ", D,
-              " and ", k_pool.size(3));
+  TORCH_CHECK((D == 64 || D == 128) && k_pool.size(3) == D, fn,
+              "D must be 64 or 128, got ", D, " and ", k_pool.size(3));
   TORCH_CHECK(Hkv >= 1 && H % Hkv == 0, fn, "H (", H,
               ") is not a multiple of Hkv (", Hkv, ")");
   TORCH_CHECK(PS == 32 || PS == 64 || PS == 128 || PS == 256, fn,
@@ -517,19 +517,26 @@ std::vector<torch::Tensor> flash_attn_verify_paged(
 
   auto stream = hetu_current_stream();
   const dim3 grid((unsigned)ns, (unsigned)Hkv, (unsigned)(B + 1));
-#define VF_LAUNCH(MM)                                                      \
-  hipLaunchKernelGGL((fa_verify_paged_kernel<MM>), grid, dim3(DM_THREADS), \
-                     0, stream, a)
-  if (mt == 1) VF_LAUNCH(1);
-  else if (mt == 2) VF_LAUNCH(2);
-  else VF_LAUNCH(DM_MAX_MT);
+#define VF_LAUNCH(MM, DD)                                                  \
+  hipLaunchKernelGGL((fa_verify_paged_kernel<MM, DD>), grid,               \
+                     dim3(DM_THREADS), 0, stream, a)
+#define VF_LAUNCH_D(DD)                                                    \
+  do {                                                                     \
+    if (mt == 1) VF_LAUNCH(1, DD);                                         \
+    else if (mt == 2) VF_LAUNCH(2, DD);                                    \
+    else VF_LAUNCH(DM_MAX_MT, DD);                                         \
+    HIP_CHECK(hipGetLastError());                                          \
+    if (ns > 1) {                                                          \
+      hipLaunchKernelGGL(fa_verify_merge_kernel<DD>,                       \
+                         dim3((unsigned)(T * H)), dim3(DD), 0, stream,     \
+                         a.ws_o, a.ws_lse, a.out, a.lse, a.cu_q, a.B, a.T, \
+                         a.H, ns);                                         \
+      HIP_CHECK(hipGetLastError());                                        \
+    }                                                                      \
+  } while (0)
+  if (D == 128) VF_LAUNCH_D(128);
+  else VF_LAUNCH_D(64);
+#undef VF_LAUNCH_D
 #undef VF_LAUNCH
-  HIP_CHECK(hipGetLastError());
-  if (ns > 1) {
-    hipLaunchKernelGGL(fa_verify_merge_kernel, dim3((unsigned)(T * H)),
-                       dim3(VF_D), 0, stream, a.ws_o, a.ws_lse, a.out, a.lse,
-                       a.cu_q, a.B, a.T, a.H, ns);
-    HIP_CHECK(hipGetLastError());
-  }
   return {out, lse};
 }

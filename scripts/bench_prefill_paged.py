@@ -14,13 +14,20 @@ Sides per row:
   varlen    context 0 and H == Hkv only: F.varlen_attention_fwd on the same
             packed rows, the same arithmetic without the table, so the
             difference is what paging and the (token, head) rows cost
+  torch     --head-dim 64 only, in place of gather: impl="torch", what these
+            inputs ran before the kernel served D = 64 (the fp32 loop over
+            sequences that reads cu_q and kv_len on the host)
+
+kernel_TBps counts the pages a call must read (K and V of every sequence's
+keys, once per KV head) over the kernel's median.
 
 Rows: "ragged" = 16 prompts of 200-2000 tokens from a fixed seed at context
 0; "chunk/C" = a 512-token chunk per sequence (--batch sequences) behind C
 cached keys.  Needs a GPU; prints one JSON line per row.
 
     python scripts/bench_prefill_paged.py [--shapes 32/8,32/32]
-        [--contexts 0,2048,8192] [--batch 8] [--page 64] [--md FILE]
+        [--contexts 0,2048,8192] [--batch 8] [--page 64] [--head-dim 128]
+        [--md FILE]
 """
 import argparse
 import json
@@ -41,6 +48,7 @@ D = 128
 
 def run_row(name, H, Hkv, PS, seqs, iters, rounds, dev, seed=0):
     """seqs: (context, n) per sequence."""
+    base = "gather" if D == 128 else "torch"
     g = torch.Generator(device=dev).manual_seed(seed)
     B = len(seqs)
     lens = [c + n for c, n in seqs]
@@ -78,14 +86,21 @@ def run_row(name, H, Hkv, PS, seqs, iters, rounds, dev, seed=0):
             outs.append(F.flash_attn_fwd(qb.contiguous(), kd.contiguous(),
                                          vd.contiguous(), True, scale)[0])
         return outs
-    sides = {"kernel": kernel, "gather": gather}
+
+    def torch_side():
+        return F.flash_attn_prefill_paged(q, kp, vp, table, cu_q, kv_len,
+                                          scale, max_q=max_q, impl="torch")
+    sides = {"kernel": kernel, base: gather if D == 128 else torch_side}
     res = {"bench": "prefill_paged", "row": name, "H": H, "Hkv": Hkv,
-           "PS": PS, "B": B, "T": T, "kv_total": sum(lens)}
+           "D": D, "PS": PS, "B": B, "T": T, "kv_total": sum(lens)}
     got = kernel()[0]
-    want = torch.cat([o[0].permute(1, 0, 2) for o in gather()])
-    res["max_abs_diff_vs_gather"] = round(
+    if D == 128:
+        want = torch.cat([o[0].permute(1, 0, 2) for o in gather()])
+    else:
+        want = torch_side()[0]
+    res["max_abs_diff_vs_" + base] = round(
         (got.float() - want.float()).abs().max().item(), 5)
-    if H == Hkv and all(c == 0 for c, _ in seqs):
+    if D == 128 and H == Hkv and all(c == 0 for c, _ in seqs):
         # the packed new rows are the pools' content, laid out densely
         kd = torch.cat([kp[table[b, :need[b]].long()].permute(1, 0, 2, 3)
                         .reshape(Hkv, -1, D)[:, :lens[b]].permute(1, 0, 2)
@@ -103,7 +118,9 @@ def run_row(name, H, Hkv, PS, seqs, iters, rounds, dev, seed=0):
             times[s].append(window_ms(fn, iters))
     for s, ts in times.items():
         res[s + "_ms"] = stats(ts)
-    res["kernel_vs_gather"] = relation(times["kernel"], times["gather"])
+    res["kernel_TBps"] = round(2 * sum(lens) * Hkv * D * 2
+                               / res["kernel_ms"]["median"] / 1e9, 3)
+    res["kernel_vs_" + base] = relation(times["kernel"], times[base])
     if "varlen" in times:
         res["kernel_vs_varlen"] = relation(times["kernel"], times["varlen"])
     print(json.dumps(res), flush=True)
@@ -114,14 +131,19 @@ def md_table(rows):
     def rng(d):
         return f"{d['median']:.4f} [{d['min']:.4f}-{d['max']:.4f}]" \
             if d else "-"
-    head = ["row", "H/Hkv", "B", "T", "keys", "kernel ms", "gather ms",
-            "kernel vs gather", "varlen ms", "kernel vs varlen"]
+    base = "gather" if D == 128 else "torch"
+    head = ["row", "H/Hkv", "B", "T", "keys", "kernel ms", base + " ms",
+            "kernel vs " + base, "varlen ms", "kernel vs varlen"]
+    if D != 128:
+        head[-2:] = ["kernel TB/s"]
     out = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
     for r in rows:
         cells = [r["row"], f"{r['H']}/{r['Hkv']}", r["B"], r["T"],
-                 r["kv_total"], rng(r["kernel_ms"]), rng(r["gather_ms"]),
-                 r["kernel_vs_gather"], rng(r.get("varlen_ms")),
+                 r["kv_total"], rng(r["kernel_ms"]), rng(r[base + "_ms"]),
+                 r["kernel_vs_" + base], rng(r.get("varlen_ms")),
                  r.get("kernel_vs_varlen", "-")]
+        if D != 128:
+            cells[-2:] = [r["kernel_TBps"]]
         out.append("| " + " | ".join(str(c) for c in cells) + " |")
     return "\n".join(out) + "\n"
 
@@ -134,8 +156,11 @@ def main():
     ap.add_argument("--contexts", default="0,2048,8192")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--page", type=int, default=64)
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128))
     ap.add_argument("--md", default="", help="also write a markdown table")
     args = ap.parse_args()
+    global D
+    D = args.head_dim
     if not torch.cuda.is_available():
         sys.exit("bench_prefill_paged: needs a GPU")
     dev = torch.device("cuda", 0)

@@ -15,13 +15,16 @@ Sides per row (B sequences, a chunk of n tokens at the end of kv_len keys):
             kv_len - n + 1 .. kv_len: what a generator without verification
             pays for n tokens
   decode    one S = 1 decode call on the same cache: the bandwidth floor
+  torch     --head-dim 64 only: impl="torch", what these inputs ran before the
+            kernels served D = 64
 
 TB/s counts the cache bytes of the step (K and V of kv_len keys per sequence
 and KV head) over the split side's median.  Needs a GPU; prints one JSON line
 per row.
 
     python scripts/bench_verify_paged.py [--shapes 32/8,32/32] [--batches 1,16]
-        [--kv 2048,8192] [--chunks 2,4,8] [--page 64] [--md FILE]
+        [--kv 2048,8192] [--chunks 2,4,8] [--page 64] [--head-dim 128]
+        [--md FILE]
 """
 import argparse
 import json
@@ -67,9 +70,14 @@ def run_row(H, Hkv, PS, B, kv, n, iters, rounds, dev, seed=0):
              "prefill": lambda: packed("hip"), "decode*n": decode_n,
              "decode": lambda: F.flash_attn_decode(
                  qs[-1], kp, vp, kv_len, scale, block_table=table)[0]}
-    res = {"bench": "verify_paged", "H": H, "Hkv": Hkv, "PS": PS, "B": B,
-           "kv_len": kv, "n": n}
+    if D != 128:
+        sides["torch"] = lambda: packed("torch")
+    res = {"bench": "verify_paged", "H": H, "Hkv": Hkv, "D": D, "PS": PS,
+           "B": B, "kv_len": kv, "n": n}
     got = sides["split"]().float()
+    if D != 128:
+        res["max_abs_diff_vs_torch"] = round(
+            (got - sides["torch"]().float()).abs().max().item(), 5)
     res["max_abs_diff_vs_prefill"] = round(
         (got - sides["prefill"]().float()).abs().max().item(), 5)
     res["max_abs_diff_vs_decode"] = round(
@@ -85,7 +93,7 @@ def run_row(H, Hkv, PS, B, kv, n, iters, rounds, dev, seed=0):
         res[s + "_ms"] = stats(ts)
     cache_bytes = 2 * B * Hkv * kv * D * 2
     res["split_TBps"] = round(cache_bytes / res["split_ms"]["median"] / 1e9, 3)
-    for s in SIDES[1:]:
+    for s in list(sides)[1:]:
         res["split_vs_" + s] = relation(times["split"], times[s])
     print(json.dumps(res), flush=True)
     return res
@@ -94,13 +102,14 @@ def run_row(H, Hkv, PS, B, kv, n, iters, rounds, dev, seed=0):
 def md_table(rows):
     def rng(d):
         return f"{d['median']:.4f} [{d['min']:.4f}-{d['max']:.4f}]"
-    head = ["H/Hkv", "B", "kv_len", "n"] + [s + " ms" for s in SIDES] + \
-        ["split TB/s"] + ["split vs " + s for s in SIDES[1:]]
+    sides = SIDES if D == 128 else SIDES + ("torch",)
+    head = ["H/Hkv", "B", "kv_len", "n"] + [s + " ms" for s in sides] + \
+        ["split TB/s"] + ["split vs " + s for s in sides[1:]]
     out = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
     for r in rows:
         cells = [f"{r['H']}/{r['Hkv']}", r["B"], r["kv_len"], r["n"]] + \
-            [rng(r[s + "_ms"]) for s in SIDES] + [r["split_TBps"]] + \
-            [r["split_vs_" + s] for s in SIDES[1:]]
+            [rng(r[s + "_ms"]) for s in sides] + [r["split_TBps"]] + \
+            [r["split_vs_" + s] for s in sides[1:]]
         out.append("| " + " | ".join(str(c) for c in cells) + " |")
     return "\n".join(out) + "\n"
 
@@ -114,8 +123,11 @@ def main():
     ap.add_argument("--kv", default="2048,8192")
     ap.add_argument("--chunks", default="2,4,8")
     ap.add_argument("--page", type=int, default=64)
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128))
     ap.add_argument("--md", default="", help="also write a markdown table")
     args = ap.parse_args()
+    global D
+    D = args.head_dim
     if not torch.cuda.is_available():
         sys.exit("bench_verify_paged: needs a GPU")
     dev = torch.device("cuda", 0)
