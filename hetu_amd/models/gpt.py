@@ -94,7 +94,7 @@ class GPTAttention(Module):
         spec = self.spec
         hl, dh = self.h_local, self.dh
         qkv = self.wqkv(x)
-        if spec.cp == 1 and dh == 128 and os.environ.get(
+        if spec.cp == 1 and dh in (64, 128) and os.environ.get(
                 "HETU_AMD_FUSED_ATTN", "1") == "1":
             # fused path: attention reads q/k/v straight out of the qkv
             # GEMM output; no slice/transpose copies (the CPU fallback

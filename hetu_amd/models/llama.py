@@ -96,7 +96,7 @@ class LlamaAttention(Module):
         qkv = self.wqkv(x)                       # [B,S,(h+2kv)*dh / tp]
         if packed is not None:
             return self.wo(self._packed_attention(qkv, B, S, packed))
-        if spec.cp == 1 and dh == 128 and os.environ.get(
+        if spec.cp == 1 and dh in (64, 128) and os.environ.get(
                 "HETU_AMD_FUSED_ATTN", "1") == "1":
             # fused path: in-place RoPE on the q|k sections + strided
             # flash attention, zero layout copies

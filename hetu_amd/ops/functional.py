@@ -1848,7 +1848,7 @@ def varlen_attention_fwd(q, k, v, cu_seqlens, causal: bool = True,
     """Packed-varlen attention (reference ParallelAttention.cc packed
     path / FlashAttention.cu mha_varlen_fwd): q/k/v [T, H, D] with
     cu_seqlens [n+1] delimiting the packed sequences; each segment attends
-    only within itself.  On GPU (D=128, no GQA mismatch constraint): ONE
+    only within itself.  On GPU (D in (64, 128), GQA allowed): ONE
     kernel launch with device-side cu offsets — no host loop, no
     `.tolist()` sync; blocks beyond a segment's tiles exit early.
     max_seqlen (optional) only shrinks the launch grid: None sizes it by
@@ -1858,7 +1858,7 @@ def varlen_attention_fwd(q, k, v, cu_seqlens, causal: bool = True,
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     T, H, D = q.shape
-    if _use_hip("varlen", q) and D == 128:
+    if _use_hip("varlen", q) and D in (64, 128):
         cu32 = cu_seqlens.to(device=q.device, dtype=torch.int32)
         o, lse = ext().flash_attn_varlen_fwd(
             q.contiguous(), k.contiguous(), v.contiguous(), cu32,
@@ -1885,7 +1885,7 @@ def varlen_attention_bwd(dout, q, k, v, out, lse, cu_seqlens,
                          scale: Optional[float] = None,
                          max_seqlen: Optional[int] = None):
     """Backward of varlen_attention_fwd -> (dq, dk, dv), packed like
-    q/k/v.  On GPU (D=128): three launches (delta, dq, dkv) over all
+    q/k/v.  On GPU (D in (64, 128)): three launches (delta, dq, dkv) over all
     segments with device-side cu offsets — no host sync, so a packed
     step can be hipGraph-captured.  Rows that belong to no segment
     (t >= cu[-1]) come back ZERO on every path.  max_seqlen: see
@@ -1893,7 +1893,7 @@ def varlen_attention_bwd(dout, q, k, v, out, lse, cu_seqlens,
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     T, H, D = q.shape
-    if _use_hip("varlen", q) and D == 128:
+    if _use_hip("varlen", q) and D in (64, 128):
         cu32 = cu_seqlens.to(device=q.device, dtype=torch.int32)
         dq, dk, dv = ext().flash_attn_varlen_bwd(
             dout.contiguous(), q.contiguous(), k.contiguous(),

@@ -573,7 +573,7 @@ std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
                   (long long)D};
     fa2_fwd_launch((const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
                    (const bf16*)v.data_ptr(), (bf16*)o.data_ptr(),
-                   lse.data_ptr<float>(), B, H, Hkv, S, Skv, (float)scale,
+                   lse.data_ptr<float>(), B, H, Hkv, S, Skv, D, (float)scale,
                    causal, sq, skv, sq, nullptr, 0, stream);
     return {o, lse};
   }

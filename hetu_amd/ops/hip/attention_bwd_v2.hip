@@ -16,6 +16,12 @@
 // vmcnt(0) every tile, epilogues); the per-tile compute bodies and every
 // layout primitive are in attention_common.h, shared with
 // attention_bwd_v3.hip.
+//
+// D = 64: both kernels keep their grid, addressing, 2-buffer staging and
+// epilogue contract and take the D = 64 tile bodies (fa_bwd_dq_tile_d64,
+// fa_bwd_dkv_tile_d64) over fa_swz_rm64t images of FA64_DQ_BN keys /
+// FA64_DKV_BQ q rows.  The dkv kernel holds its K and V rows in registers and
+// needs no per-wave image.
 #include <torch/extension.h>
 #include "ext_stream.h"
 #include "attention_common.h"
@@ -39,10 +45,14 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
     bf16* __restrict__ dQ, int B, int H, int Hkv, int S, int Skv,
     float scale, bool causal, FaStrides sq, FaStrides skv, FaStrides sdo,
     FaStrides sdq, const int* __restrict__ cu, int lse_T, bool mask_all) {
-  static_assert(D == 128);
+  static_assert(D == 64 || D == 128);
+  constexpr int BN = D == 128 ? 64 : FA64_DQ_BN;    // keys per tile
+  constexpr int IMG = BN * 2 * D;                   // bytes of a K or V image
+  constexpr int NGLDS = IMG / (THREADS * 16);       // glds per lane and image
+  constexpr int ROW_SH = D == 128 ? 8 : 7;          // log2 of a row's bytes
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  auto k_lds = [&](int b) -> char* { return smem + b * FA_KV_IMG; };
-  auto v_lds = [&](int b) -> char* { return smem + (2 + b) * FA_KV_IMG; };
+  auto k_lds = [&](int b) -> char* { return smem + b * IMG; };
+  auto v_lds = [&](int b) -> char* { return smem + (2 + b) * IMG; };
 
   // (bh, q-block) grid: spreads causal depths across CUs (see fwd note)
   const int bh = blockIdx.x;
@@ -85,48 +95,59 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
   const float del_q = DELTA[stat0 + min(my_q, S - 1)];
 
   // Q (scaled) and dO in registers
-  bf16x8 qreg[8], doreg[8];
-  fa_load_row_frags(qreg, Qb + (int64_t)min(my_q, S - 1) * sq.rs, hi, scale);
-  fa_load_row_frags(doreg, dOb + (int64_t)min(my_q, S - 1) * sdo.rs, hi);
+  bf16x8 qreg[D / 16], doreg[D / 16];
+  fa_load_row_frags_d<D>(qreg, Qb + (int64_t)min(my_q, S - 1) * sq.rs, hi,
+                         scale);
+  fa_load_row_frags_d<D>(doreg, dOb + (int64_t)min(my_q, S - 1) * sdo.rs, hi);
 
   const int wlane16 = lane * 16;
 #define DQ_GLDS(k0, buf)                                                    \
   do {                                                                      \
     _Pragma("unroll")                                                       \
-    for (int i = 0; i < 2; ++i) {                                           \
-      int pos = (wid * 2 + i) * 1024 + wlane16;                             \
-      int64_t roff = (int64_t)min((k0) + (pos >> 8), Skv - 1) * skv.rs      \
-                   + fa_rm_src_col(pos);                                    \
+    for (int i = 0; i < NGLDS; ++i) {                                       \
+      int pos = (wid * NGLDS + i) * 1024 + wlane16;                         \
+      int64_t roff = (int64_t)min((k0) + (pos >> ROW_SH), Skv - 1) * skv.rs \
+                   + (D == 128 ? fa_rm_src_col(pos) : fa_rm64t_src_col(pos)); \
       fa_glds16(Kb + roff, k_lds(buf) + pos);                               \
       fa_glds16(Vb + roff, v_lds(buf) + pos);                               \
     }                                                                       \
   } while (0)
 
-  f32x16 dq_acc[4];
+  f32x16 dq_acc[D / 32];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
+  for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq_acc[dt][r] = 0.f;
 
   const int wave_qmax = q0 + wid * 32 + 31;
-  const int n_tiles = fa_n_kv_tiles(q0, Skv, diag, causal);
+  const int n_tiles = fa_n_kv_tiles<BN>(q0, Skv, diag, causal);
 
   DQ_GLDS(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
   for (int t = 0; t < n_tiles; ++t) {
-    const int k0 = t * 64;
+    const int k0 = t * BN;
     const int cur = t & 1;
     const bool have_next = (t + 1) < n_tiles;
-    if (have_next) DQ_GLDS(k0 + 64, cur ^ 1);
+    if (have_next) DQ_GLDS(k0 + BN, cur ^ 1);
 
     const bool active = !causal || (k0 <= wave_qmax + diag);
     if (active) {
-      const bool boundary = fa_boundary_kv_tile(wave_qmax - 31, k0, S, Skv,
-                                                diag, causal, mask_all);
-      FA_BWD_DQ_TILE(boundary, k_lds(cur), v_lds(cur), qreg, doreg, dq_acc,
-                     k0, my_q, S, Skv, diag, causal, lse_q, del_q, lane);
+      const bool boundary = fa_boundary_kv_tile<BN>(wave_qmax - 31, k0, S,
+                                                    Skv, diag, causal,
+                                                    mask_all);
+      if constexpr (D == 128) {
+        FA_BWD_DQ_TILE(boundary, k_lds(cur), v_lds(cur), qreg, doreg, dq_acc,
+                       k0, my_q, S, Skv, diag, causal, lse_q, del_q, lane);
+      } else {
+        // the last key any row of the wave sees, wave-uniform
+        const int wave_last_key = __builtin_amdgcn_readfirstlane(
+            causal ? min(Skv - 1, wave_qmax + diag) : Skv - 1);
+        fa_bwd_dq_tile_d64<BN>(boundary, k_lds(cur), v_lds(cur), qreg, doreg,
+                               dq_acc, k0, wave_last_key, my_q, S, Skv, diag,
+                               causal, lse_q, del_q, lane);
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -138,7 +159,155 @@ __global__ __launch_bounds__(THREADS, 2) void fa2_bwd_dq_kernel(
     bf16* qrow = dQ
         + (VARLEN ? (int64_t)row0 * sdq.rs : (int64_t)b * sdq.bs)
         + (int64_t)h * sdq.hs + (int64_t)my_q * sdq.rs;
-    fa_store_row_bf16(dq_acc, scale, qrow, hi);
+    fa_store_row_bf16_d<D>(dq_acc, scale, qrow, hi);
+  }
+}
+
+// ===========================================================================
+// dkv at D = 64: the block of fa2_bwd_dkv_kernel<64, *> after its addressing
+// prologue.  8 waves x 32 exclusive keys with the wave's K (scaled) and V
+// rows in registers; Q / dO stream through LDS in tiles of BQ rows together
+// with the tile's lse / delta rows, 2 buffers, vmcnt(0) drained per tile as
+// at D = 128.  A tile is walked in 32-q groups by fa_bwd_dkv_tile_d64.
+// ===========================================================================
+template <bool VARLEN>
+DEV void fa2_bwd_dkv_d64(char* smem, const bf16* Qb, const bf16* dOb,
+                         const bf16* Kb, const bf16* Vb, const float* lse_b,
+                         const float* del_b, float* dK32, float* dV32,
+                         bf16* dK16, bf16* dV16, int b, int hkv, int Hkv,
+                         int kb0, int row0, int S, int Skv, float scale,
+                         bool causal, bool gqa, FaStrides sq, FaStrides skv,
+                         FaStrides sdo, FaStrides sdkv) {
+  constexpr int BQ = FA64_DKV_BQ;             // q rows per tile
+  constexpr int IMG = BQ * 128;               // bytes of a Q or dO image
+  constexpr int NGLDS = IMG / (THREADS * 16); // glds per lane and image
+  constexpr int NSTAT = BQ / 64;              // 4-byte glds per stat row set
+  auto q_lds = [&](int i) -> char* { return smem + i * IMG; };
+  auto do_lds = [&](int i) -> char* { return smem + (2 + i) * IMG; };
+  auto lse_lds = [&](int i) -> float* {
+    return reinterpret_cast<float*>(smem + 4 * IMG) + (2 * i) * BQ;
+  };
+  auto del_lds = [&](int i) -> float* { return lse_lds(i) + BQ; };
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int hi = lane >> 5;
+  // wave-uniform copies for the skip tests and the stat staging branch
+  const int wu = __builtin_amdgcn_readfirstlane(wid);
+  const int wave_kmin = kb0 + wu * 32;
+  const int my_key = wave_kmin + (lane & 31);
+  const int diag = Skv - S;
+
+  bf16x8 kreg[4], vreg[4];
+  fa_load_row_frags_d<64>(kreg, Kb + (int64_t)min(my_key, Skv - 1) * skv.rs,
+                          hi, scale);
+  fa_load_row_frags_d<64>(vreg, Vb + (int64_t)min(my_key, Skv - 1) * skv.rs,
+                          hi);
+
+  // per tile and lane NGLDS 16-byte DMAs per image; waves 0 .. NSTAT - 1 add
+  // one 4-byte DMA of 64 lse rows, the next NSTAT waves one of delta.  Rows
+  // past S clamp to the last one (their P is masked).
+  auto stage = [&](int qt0, int buf) {
+#pragma unroll
+    for (int i = 0; i < NGLDS; ++i) {
+      const int pos = (wid * NGLDS + i) * 1024 + lane * 16;
+      const int qr = min(qt0 + (pos >> 7), S - 1);
+      const int qd = fa_rm64t_src_col(pos);
+      fa_glds16(Qb + (int64_t)qr * sq.rs + qd, q_lds(buf) + pos);
+      fa_glds16(dOb + (int64_t)qr * sdo.rs + qd, do_lds(buf) + pos);
+    }
+    if (wu < 2 * NSTAT) {
+      const int part = wu < NSTAT ? wu : wu - NSTAT;
+      const float* src = (wu < NSTAT ? lse_b : del_b) +
+                         min(qt0 + 64 * part + lane, S - 1);
+      float* dst = (wu < NSTAT ? lse_lds(buf) : del_lds(buf)) + 64 * part;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+    }
+  };
+
+  f32x16 dk_acc[2], dv_acc[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dk_acc[dt][r] = 0.f; dv_acc[dt][r] = 0.f; }
+
+  const int n_q_tiles = (S + BQ - 1) / BQ;
+  // first tile with a row that any key of the block can see
+  const int t_start = causal ? max(0, kb0 - diag) / BQ : 0;
+
+  stage(t_start * BQ, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+
+  for (int t = t_start; t < n_q_tiles; ++t) {
+    const int qt0 = t * BQ;
+    const int cur = (t - t_start) & 1;
+    if (t + 1 < n_q_tiles) stage(qt0 + BQ, cur ^ 1);
+
+    if (wave_kmin < Skv) {
+#pragma unroll
+      for (int sub = 0; sub < BQ / 32; ++sub) {
+        const int qs0 = qt0 + 32 * sub;
+        // wave-uniform: rows left, and a key of the wave that sees them
+        if (qs0 >= S) break;
+        if (causal && qs0 + 31 < wave_kmin - diag) continue;
+        fa_bwd_dkv_tile_d64(q_lds(cur), do_lds(cur), lse_lds(cur),
+                            del_lds(cur), kreg, vreg, dk_acc, dv_acc, sub,
+                            qs0, my_key, S, Skv, diag, causal, lane);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+
+  // ---- epilogue: the lane's own key row, 4 runs of 4 d per 32-d tile (the
+  // forward's O layout); dK = scale * acc; fp32 atomics under GQA ---------
+  if (gqa) {
+    // A lane owns a key row, so atomics straight from the accumulators would
+    // touch 64 rows per instruction.  The wave turns its [32 key][64 d] fp32
+    // tile through LDS instead (8 KiB of the images, dead after the loop's
+    // last barrier) and adds with lane = d: one 256-B row per instruction.
+    // The 16-B column c of row k is stored at c ^ (k & 15): the 16 lanes a
+    // ds_write_b128 serves at a time hold 16 consecutive keys and one c,
+    // hence 16 distinct columns; a read takes the 64 floats of one row, every
+    // bank once.
+    float* tw = reinterpret_cast<float*>(smem) + wu * (32 * 64);
+    const int iq = lane & 31;
+    const int64_t base32 =
+        (VARLEN ? ((int64_t)(row0 + wave_kmin) * Hkv + hkv)
+                : ((int64_t)(b * Hkv + hkv) * Skv + wave_kmin)) * 64;
+    const int64_t rstride = VARLEN ? (int64_t)Hkv * 64 : 64;
+    const int nrow = min(32, Skv - wave_kmin);
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      const f32x16 (&acc)[2] = pass ? dv_acc : dk_acc;
+      const float mul = pass ? 1.f : scale;
+      float* dst = (pass ? dV32 : dK32) + base32 + lane;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int c = (8 * dt + 2 * g + hi) ^ (iq & 15);
+          *reinterpret_cast<float4*>(tw + iq * 64 + c * 4) = make_float4(
+              acc[dt][4 * g + 0] * mul, acc[dt][4 * g + 1] * mul,
+              acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll 4
+      for (int r = 0; r < nrow; ++r)
+        atomicAdd(dst + r * rstride,
+                  tw[r * 64 + ((((lane >> 2) ^ (r & 15)) << 2) | (lane & 3))]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+  } else if (my_key < Skv) {
+    const int64_t off =
+        (VARLEN ? (int64_t)row0 * sdkv.rs : (int64_t)b * sdkv.bs)
+        + (int64_t)hkv * sdkv.hs + (int64_t)my_key * sdkv.rs;
+    fa_store_row_bf16_d<64>(dk_acc, scale, dK16 + off, hi);
+    fa_store_row_bf16_d<64>(dv_acc, 1.f, dV16 + off, hi);
   }
 }
 
@@ -156,12 +325,8 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
     int B, int H, int Hkv, int S, int Skv, float scale, bool causal,
     FaStrides sq, FaStrides skv, FaStrides sdo, FaStrides sdkv,
     const int* __restrict__ cu, int lse_T) {
-  static_assert(D == 128);
+  static_assert(D == 64 || D == 128);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  auto q_lds = [&](int b) -> char* { return smem + b * FA_Q_IMG; };
-  auto do_lds = [&](int b) -> char* { return smem + (2 + b) * FA_Q_IMG; };
-  char* vw_base = smem + 4 * FA_Q_IMG;             // per-wave V images
-  char* pw_base = vw_base + 8 * FA_WAVE_V_IMG;     // per-wave P'/dS' pairs
 
   // (bh, kv-block) grid: spreads causal depths across CUs (see fwd note)
   const int bh = blockIdx.x;
@@ -202,86 +367,96 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_bwd_dkv_kernel(
   const int my_key = wave_kmin + iq;           // lane's exclusive key row
   const int diag = Skv - S;
 
-  char* vw_lds = vw_base + wid * FA_WAVE_V_IMG;
-  char* p_lds = pw_base + wid * 2 * FA_P_IMG;
+  if constexpr (D == 128) {
+    auto q_lds = [&](int b) -> char* { return smem + b * FA_Q_IMG; };
+    auto do_lds = [&](int b) -> char* { return smem + (2 + b) * FA_Q_IMG; };
+    char* vw_base = smem + 4 * FA_Q_IMG;             // per-wave V images
+    char* pw_base = vw_base + 8 * FA_WAVE_V_IMG;     // per-wave P'/dS' pairs
+    char* vw_lds = vw_base + wid * FA_WAVE_V_IMG;
+    char* p_lds = pw_base + wid * 2 * FA_P_IMG;
 
-  // K (scaled) in registers; V in a per-wave swizzled row-major LDS image
-  // (keeps the VGPR budget at 2 waves/SIMD without spills)
-  bf16x8 kreg[8];
-  fa_load_row_frags(kreg, Kb + (int64_t)min(my_key, Skv - 1) * skv.rs, hi,
-                    scale);
-  fa_stage_wave_v(Vb, skv.rs, wave_kmin, Skv, vw_lds, lane);
+    // K (scaled) in registers; V in a per-wave swizzled row-major LDS image
+    // (keeps the VGPR budget at 2 waves/SIMD without spills)
+    bf16x8 kreg[8];
+    fa_load_row_frags(kreg, Kb + (int64_t)min(my_key, Skv - 1) * skv.rs, hi,
+                      scale);
+    fa_stage_wave_v(Vb, skv.rs, wave_kmin, Skv, vw_lds, lane);
 
-  // per tile: Qrm 8 KiB + dOrm 8 KiB; 512 lanes x 16 B covers 8 KiB, so one
-  // glds per lane per image.
+    // per tile: Qrm 8 KiB + dOrm 8 KiB; 512 lanes x 16 B covers 8 KiB, so one
+    // glds per lane per image.
 #define DKV_GLDS(qt0, buf)                                                  \
-  do {                                                                      \
-    int pos = tid * 16;                                                     \
-    int qr_ = min((qt0) + (pos >> 8), S - 1);                               \
-    int qd = fa_rm_src_col(pos);                                            \
-    fa_glds16(Qb + (int64_t)qr_ * sq.rs + qd, q_lds(buf) + pos);            \
-    fa_glds16(dOb + (int64_t)qr_ * sdo.rs + qd, do_lds(buf) + pos);         \
-  } while (0)
+    do {                                                                      \
+      int pos = tid * 16;                                                     \
+      int qr_ = min((qt0) + (pos >> 8), S - 1);                               \
+      int qd = fa_rm_src_col(pos);                                            \
+      fa_glds16(Qb + (int64_t)qr_ * sq.rs + qd, q_lds(buf) + pos);            \
+      fa_glds16(dOb + (int64_t)qr_ * sdo.rs + qd, do_lds(buf) + pos);         \
+    } while (0)
 
-  f32x16 dk_acc[4], dv_acc[4];
+    f32x16 dk_acc[4], dv_acc[4];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { dk_acc[dt][r] = 0.f; dv_acc[dt][r] = 0.f; }
+      for (int r = 0; r < 16; ++r) { dk_acc[dt][r] = 0.f; dv_acc[dt][r] = 0.f; }
 
-  const int n_q_tiles = (S + 31) / 32;
-  const int t_start = fa_first_q_tile(kb0, diag, causal);
+    const int n_q_tiles = (S + 31) / 32;
+    const int t_start = fa_first_q_tile(kb0, diag, causal);
 
-  DKV_GLDS(t_start * 32, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  for (int t = t_start; t < n_q_tiles; ++t) {
-    const int qt0 = t * 32;
-    const int cur = (t - t_start) & 1;
-    const bool have_next = (t + 1) < n_q_tiles;
-    if (have_next) DKV_GLDS(qt0 + 32, cur ^ 1);
-
-    // wave active if any of its keys can see this q tile
-    const bool active = !causal || (qt0 + 31 >= wave_kmin - diag);
-    if (active)
-      fa_bwd_dkv_tile(q_lds(cur), do_lds(cur), vw_lds, p_lds, kreg, dk_acc,
-                      dv_acc, qt0, wave_kmin, S, Skv, diag, causal, lse_b,
-                      del_b, lane);
+    DKV_GLDS(t_start * 32, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-  }
+
+    for (int t = t_start; t < n_q_tiles; ++t) {
+      const int qt0 = t * 32;
+      const int cur = (t - t_start) & 1;
+      const bool have_next = (t + 1) < n_q_tiles;
+      if (have_next) DKV_GLDS(qt0 + 32, cur ^ 1);
+
+      // wave active if any of its keys can see this q tile
+      const bool active = !causal || (qt0 + 31 >= wave_kmin - diag);
+      if (active)
+        fa_bwd_dkv_tile(q_lds(cur), do_lds(cur), vw_lds, p_lds, kreg, dk_acc,
+                        dv_acc, qt0, wave_kmin, S, Skv, diag, causal, lse_b,
+                        del_b, lane);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
 #undef DKV_GLDS
 
-  // ---- epilogue: dK = scale * acc; plain stores unless GQA -------------
-  const bool gqa = (H != Hkv);
+    // ---- epilogue: dK = scale * acc; plain stores unless GQA -------------
+    const bool gqa = (H != Hkv);
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int key = wave_kmin + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      if (key < Skv) {
-        float dkv_ = dk_acc[dt][r] * scale;
-        float dvv_ = dv_acc[dt][r];
-        if (gqa) {
-          // f32 accumulation buffers: BHSD-contiguous (dense) or packed
-          // [T, Hkv, D] (varlen)
-          int64_t off32 =
-              (VARLEN ? ((int64_t)(row0 + key) * Hkv + hkv)
-                      : ((int64_t)(b * Hkv + hkv) * Skv + key)) * D
-              + 32 * dt + iq;
-          atomicAdd(dK32 + off32, dkv_);
-          atomicAdd(dV32 + off32, dvv_);
-        } else {
-          int64_t off =
-              (VARLEN ? (int64_t)row0 * sdkv.rs : (int64_t)b * sdkv.bs)
-              + (int64_t)hkv * sdkv.hs + (int64_t)key * sdkv.rs
-              + 32 * dt + iq;
-          dK16[off] = (bf16)dkv_;
-          dV16[off] = (bf16)dvv_;
+      for (int r = 0; r < 16; ++r) {
+        int key = wave_kmin + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (key < Skv) {
+          float dkv_ = dk_acc[dt][r] * scale;
+          float dvv_ = dv_acc[dt][r];
+          if (gqa) {
+            // f32 accumulation buffers: BHSD-contiguous (dense) or packed
+            // [T, Hkv, D] (varlen)
+            int64_t off32 =
+                (VARLEN ? ((int64_t)(row0 + key) * Hkv + hkv)
+                        : ((int64_t)(b * Hkv + hkv) * Skv + key)) * D
+                + 32 * dt + iq;
+            atomicAdd(dK32 + off32, dkv_);
+            atomicAdd(dV32 + off32, dvv_);
+          } else {
+            int64_t off =
+                (VARLEN ? (int64_t)row0 * sdkv.rs : (int64_t)b * sdkv.bs)
+                + (int64_t)hkv * sdkv.hs + (int64_t)key * sdkv.rs
+                + 32 * dt + iq;
+            dK16[off] = (bf16)dkv_;
+            dV16[off] = (bf16)dvv_;
+          }
         }
       }
     }
+  } else {
+    fa2_bwd_dkv_d64<VARLEN>(smem, Qb, dOb, Kb, Vb, lse_b, del_b, dK32, dV32,
+                            dK16, dV16, b, hkv, Hkv, kb0, row0, S, Skv, scale,
+                            causal, H != Hkv, sq, skv, sdo, sdkv);
   }
 }
 
@@ -295,7 +470,32 @@ __global__ void fa2_delta_kernel(const bf16* __restrict__ dO,
   // D == 128 fast path: 4 lanes per row (32 elems each, 16B vector
   // loads), quad shuffle reduction — pure bandwidth (the old one-block-
   // per-row version left 240/256 lanes idle: 580us vs the ~65us bound).
+  // D == 64 takes the same path with 16 elems per lane.
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (D == 64) {
+    int64_t row = tid >> 2;
+    const int q = tid & 3;
+    const int64_t rstride = ((int64_t)gridDim.x * blockDim.x) >> 2;
+    for (; row < rows; row += rstride) {
+      const int64_t b = row / ((int64_t)H * S);
+      const int64_t hh = (row / S) % H;
+      const int64_t ss = row % S;
+      const int64_t base = b * so.bs + hh * so.hs + ss * so.rs + q * 16;
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; i += 8) {
+        float av[8], bv[8];
+        VecIO<bf16>::load(dO + base + i, av);
+        VecIO<bf16>::load(O + base + i, bv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += av[j] * bv[j];
+      }
+      s += __shfl_xor(s, 1);
+      s += __shfl_xor(s, 2);
+      if (q == 0) delta[row] = s;
+    }
+    return;
+  }
   if (D == 128) {
     int64_t row = tid >> 2;
     const int q = tid & 3;
@@ -342,18 +542,23 @@ void fa2_bwd_kernels(const bf16* doutp, const bf16* qp, const bf16* kp,
                      const bf16* vp, const float* lse, const float* delta,
                      bf16* dqp, bf16* dk16p, bf16* dv16p, float* dk32p,
                      float* dv32p, int B, int H, int Hkv, int S, int Skv,
-                     bool causal, float scale, FaStrides sq, FaStrides skv,
-                     FaStrides sdo, FaStrides sdq, FaStrides sdkv,
+                     int D, bool causal, float scale, FaStrides sq,
+                     FaStrides skv, FaStrides sdo, FaStrides sdq,
+                     FaStrides sdkv,
                      const int* cu, int lse_T, hipStream_t stream) {
   const bool mask_all = fa_mask_all();
-  hipLaunchKernelGGL((fa2_bwd_dq_kernel<128, VARLEN>),
-                     dim3(B * H, (S + 255) / 256), dim3(THREADS), FA2_DQ_LDS,
-                     stream, qp, kp, vp, doutp, lse, delta, dqp, B, H, Hkv,
-                     S, Skv, scale, causal, sq, skv, sdo, sdq, cu, lse_T,
-                     mask_all);
-  hipLaunchKernelGGL((fa2_bwd_dkv_kernel<128, VARLEN>),
-                     dim3(B * H, (Skv + 255) / 256), dim3(THREADS),
-                     FA_DKV_LDS, stream, qp, kp, vp, doutp, lse, delta,
+  TORCH_CHECK(D == 64 || D == 128, "fa2 bwd: D must be 64 or 128, got ", D);
+  auto dq_kernel = D == 128 ? fa2_bwd_dq_kernel<128, VARLEN>
+                            : fa2_bwd_dq_kernel<64, VARLEN>;
+  auto dkv_kernel = D == 128 ? fa2_bwd_dkv_kernel<128, VARLEN>
+                             : fa2_bwd_dkv_kernel<64, VARLEN>;
+  hipLaunchKernelGGL(dq_kernel, dim3(B * H, (S + 255) / 256), dim3(THREADS),
+                     D == 128 ? FA2_DQ_LDS : FA64_DQ_LDS, stream, qp, kp, vp,
+                     doutp, lse, delta, dqp, B, H, Hkv, S, Skv, scale, causal,
+                     sq, skv, sdo, sdq, cu, lse_T, mask_all);
+  hipLaunchKernelGGL(dkv_kernel, dim3(B * H, (Skv + 255) / 256),
+                     dim3(THREADS), D == 128 ? FA_DKV_LDS : FA64_DKV_LDS,
+                     stream, qp, kp, vp, doutp, lse, delta,
                      dk32p, dv32p, dk16p, dv16p, B, H, Hkv, S, Skv, scale,
                      causal, sq, skv, sdo, sdkv, cu, lse_T);
 }
@@ -379,7 +584,7 @@ void fa2_bwd_core(const bf16* doutp, const bf16* qp, const bf16* kp,
                   sdo, stream);
   auto launch = cu ? fa2_bwd_kernels<true> : fa2_bwd_kernels<false>;
   launch(doutp, qp, kp, vp, lse.data_ptr<float>(), delta.data_ptr<float>(),
-         dqp, dk16p, dv16p, dk32p, dv32p, B, H, Hkv, S, Skv, causal, scale,
+         dqp, dk16p, dv16p, dk32p, dv32p, B, H, Hkv, S, Skv, D, causal, scale,
          sq, skv, sdo, sdq, sdkv, cu, lse_T, stream);
 }
 
@@ -458,7 +663,8 @@ std::vector<torch::Tensor> flash_attn_varlen_bwd(
               cu.is_contiguous(), "varlen: cu int32 on device");
   const int T = q.size(0), H = q.size(1), D = q.size(2);
   const int Hkv = k.size(1);
-  TORCH_CHECK(D == 128, "fa2 varlen: D=128 only");
+  TORCH_CHECK(D == 64 || D == 128,
+              "fa2 varlen: D must be 64 or 128, got ", D);
   TORCH_CHECK(k.dim() == 3 && k.size(0) == T && k.size(2) == D &&
               v.sizes() == k.sizes() && Hkv > 0 && H % Hkv == 0,
               "varlen: k/v [T, Hkv, D]");
@@ -491,6 +697,7 @@ torch::Tensor flash_attn_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                                  bool causal, double scale) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous());
   TORCH_CHECK(dout.is_contiguous() && out.is_contiguous());
+  TORCH_CHECK(D == 64 || D == 128, "fa2 qkv: D must be 64 or 128, got ", D);
   const int B = qkv.size(0), S = qkv.size(1);
   const int64_t C = (H + 2 * Hkv) * D;
   const bool gqa = (H != Hkv);

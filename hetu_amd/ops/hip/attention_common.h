@@ -36,6 +36,26 @@ constexpr size_t FA3_DQ_LDS = 2 * FA_RING * (size_t)FA_KV_IMG;    // 96 KiB
 constexpr size_t FA_DKV_LDS =
     4 * (size_t)FA_Q_IMG + 8 * (size_t)FA_WAVE_V_IMG + 8 * 2 * (size_t)FA_P_IMG;
 
+// v2 backward at D = 64 (rows of 128 B).  Both kernels walk their tile in
+// 32-row groups, so the tile length is only a loop count and an image size:
+// 64 or 128 rows.  128 is built; FA64_* can be set to 64 on the compiler's
+// command line to compile the other one (docs/KERNELS.md has both reports).
+#ifndef FA64_DQ_BN
+#define FA64_DQ_BN 128       // keys per K / V image of the dq kernel
+#endif
+#ifndef FA64_DKV_BQ
+#define FA64_DKV_BQ 128      // q rows per Q / dO image of the dkv kernel
+#endif
+// dq: 2 buffers x (K, V) images
+constexpr size_t FA64_DQ_LDS = 2 * 2 * (size_t)FA64_DQ_BN * 128;  // 64 KiB
+// dkv: 2 buffers x (Q, dO) images, then 2 x (lse, delta) rows of the tile;
+// the GQA epilogue reuses the front as 8 per-wave [32 key][64 d] fp32 tiles
+constexpr size_t FA64_DKV_TURN = 8 * 32 * 64 * sizeof(float);     // 64 KiB
+constexpr size_t FA64_DKV_IMGS = 2 * 2 * (size_t)FA64_DKV_BQ * 128;
+constexpr size_t FA64_DKV_LDS =
+    (FA64_DKV_IMGS > FA64_DKV_TURN ? FA64_DKV_IMGS : FA64_DKV_TURN) +
+    2 * 2 * (size_t)FA64_DKV_BQ * 4;
+
 DEV int fa_swz_rm(int row, int byte_in_row) {
   return row * 256 + (byte_in_row ^ ((row & 15) << 4));
 }
@@ -310,6 +330,24 @@ DEV void fa_load_row_frags_d(bf16x8 (&frags)[D / 16], const bf16* row,
     frags[kk] = *reinterpret_cast<const bf16x8*>(row + kk * 16 + hi * 8);
 }
 
+// the scaled form (softmax scale folded into Q or K, rounded to bf16)
+template <int D>
+DEV void fa_load_row_frags_d(bf16x8 (&frags)[D / 16], const bf16* row, int hi,
+                             float scale) {
+  if constexpr (D == 128) {
+    fa_load_row_frags(frags, row, hi, scale);
+  } else {
+#pragma unroll
+    for (int kk = 0; kk < D / 16; ++kk) {
+      ushort8 u = *reinterpret_cast<const ushort8*>(row + kk * 16 + hi * 8);
+      union { ushort8 us; bf16x8 v; } cvt;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) cvt.us.v[j] = f2bf(bf2f(u.v[j]) * scale);
+      frags[kk] = cvt.v;
+    }
+  }
+}
+
 // O epilogue over D / 32 accumulator tiles (fa_store_row_bf16's layout)
 template <int D>
 DEV void fa_store_row_bf16_d(const f32x16 (&acc)[D / 32], float mul,
@@ -337,10 +375,13 @@ DEV void fa_stage_wave_v(const bf16* Vb, int64_t row_stride, int key0,
 }
 
 // ---- causal tile bounds ---------------------------------------------------
-// diag = Skv - S.  Number of 64-key tiles the 256-row q block at q0 visits:
+// diag = Skv - S.  BN is the key count of a tile: 64 at D = 128, and the
+// forward's and dq's 128 at D = 64.  Number of BN-key tiles the 256-row q
+// block at q0 visits:
+template <int BN = 64>
 DEV int fa_n_kv_tiles(int q0, int Skv, int diag, bool causal) {
-  const int n = (Skv + 63) / 64;
-  return causal ? min(n, max((q0 + 256 + diag + 63) / 64, 1)) : n;
+  const int n = (Skv + BN - 1) / BN;
+  return causal ? min(n, max((q0 + 256 + diag + BN - 1) / BN, 1)) : n;
 }
 // First 32-row q tile that any key of the 256-key block at kb0 can see:
 DEV int fa_first_q_tile(int kb0, int diag, bool causal) {
@@ -352,15 +393,16 @@ DEV int fa_first_q_tile(int kb0, int diag, bool causal) {
 // 32 rows; everywhere else every select of the mask is false and the plain
 // stage computes the same bits without them.  Wave-uniform.  mask_all
 // (HETU_AMD_FA_MASK_ALL=1) forces the masked stage.  Rows qw0..qw0+31
-// against the 64-key tile at k0:
+// against the BN-key tile at k0 (its last key is k0 + BN - 1):
+template <int BN = 64>
 DEV bool fa_boundary_kv_tile(int qw0, int k0, int S, int Skv, int diag,
                              bool causal, bool mask_all) {
   qw0 = __builtin_amdgcn_readfirstlane(qw0);    // the wave index is a VGPR
-  return mask_all || (k0 + 63 >= Skv) || (qw0 + 31 >= S) ||
-         (causal && k0 + 63 > qw0 + diag);
+  return mask_all || (k0 + BN - 1 >= Skv) || (qw0 + 31 >= S) ||
+         (causal && k0 + BN - 1 > qw0 + diag);
 }
 // The masked bodies.  In the C layout register r of a lane holds key
-// kbase + 4*hi + fa_crow(r) (+32 for a tile's second 32-key half).  The
+// kbase + 4*hi + fa_crow(r) (+32 ct for a tile's 32-key block ct).  The
 // three tests (key tail, row tail, causal diagonal) fold into one per-lane
 // bound, so an element costs a single compare against a constant:
 // masked iff 4*hi-relative key index > fa_mask_bound(kbase + 4*hi, ...).
@@ -510,6 +552,197 @@ DEV void fa_bwd_dkv_tile(const char* q_img, const char* do_img,
   }
 }
 
+// ---- backward tile bodies at D = 64 ---------------------------------------
+// Row-major image of the D = 64 backward: [rows][128 B], the 16-B slot s of
+// row r stored at slot s ^ f(r), f(r) = ((r >> 1) & 1) << 2 | ((r >> 2) & 3).
+// Each image is read two ways, and f is chosen so that neither conflicts
+// (64 banks of 4 B, a 256-B bank line that holds rows 2l and 2l + 1; derived
+// from this arithmetic, not measured with counters):
+//  * ds_read_b128, A-fragments of S^T / dP^T: served 16 lanes at a time, the
+//    16 lanes read one slot s of rows r0 .. r0 + 15, r0 a multiple of 16.
+//    Over those rows ((r >> 1) & 7) takes all 8 values and f permutes its
+//    bits, so the 8 row pairs get 8 distinct slots and the two rows of a pair
+//    lie in the two halves of the line: 16 distinct 16-B columns, every bank
+//    once.  (fa_swz_rm_d<64> has this property too.)
+//  * ds_read_b64_tr_b16, the transposed fragments: served 32 lanes at a time;
+//    a half wave reads 64 contiguous source bytes (slots 4 dt .. 4 dt + 3) of
+//    rows R .. R + 3, R a multiple of 4.  Bits 0-1 of f permute the slots
+//    inside that 64-B window, bit 2 selects the window.  Rows R, R + 1 share
+//    f and lie in different halves of a line; rows R + 2, R + 3 have bit 2 of
+//    f flipped ((r >> 1) & 1 changes), so they take the other window of their
+//    halves: 4 x 64 B on 4 distinct quarters of the bank line, every bank
+//    once.  fa_swz_rm_d<64> fails here (its XOR of rows R + 2 differs from
+//    that of R in bit 0 only: same window, a 2-way conflict), which is why
+//    the backward has a swizzle of its own.
+// f(r) is unchanged by r + 16 and f(r + 4) = f(r) ^ 1 where (r >> 2) is even,
+// so of the 8 reads of a block only 4 addresses differ.
+DEV int fa_f64(int row) {
+  return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
+}
+DEV int fa_swz_rm64t(int row, int byte_in_row) {
+  return row * 128 + (byte_in_row ^ (fa_f64(row) << 4));
+}
+// inverse for staging: source element column of linear image byte `pos`
+// (row = pos >> 7; a 1 KiB DMA instruction is 8 rows)
+DEV int fa_rm64t_src_col(int pos) {
+  return ((pos & 127) ^ (fa_f64(pos >> 7) << 4)) >> 1;
+}
+
+// The transposed fragments d[s][dt] (own = column 32 dt + iq, k = 8 rows at
+// rowb + 16 s + 8 hi ..) of the 32 rows at rowb (a multiple of 32) of a
+// fa_swz_rm64t image: 8 reads under one lgkmcnt wait, 4 MFMA operands.
+DEV void fa_tr_rm64t_2x2(bf16x8 (&d)[2][2], const char* img, int rowb,
+                         int lane) {
+  const int r1 = rowb + 8 * (lane >> 5) + ((lane >> 2) & 3);
+  const int m1 = fa_f64(r1) << 4;
+  const int cb0 = fa_tr_colbyte(lane);
+  const unsigned b1 = fa_lds_addr(img + r1 * 128);
+  u32x2 x[8];
+  asm volatile("ds_read_b64_tr_b16 %0, %8\n\t"
+               "ds_read_b64_tr_b16 %1, %9\n\t"
+               "ds_read_b64_tr_b16 %2, %10\n\t"
+               "ds_read_b64_tr_b16 %3, %11\n\t"
+               "ds_read_b64_tr_b16 %4, %8 offset:2048\n\t"
+               "ds_read_b64_tr_b16 %5, %9 offset:2048\n\t"
+               "ds_read_b64_tr_b16 %6, %10 offset:2048\n\t"
+               "ds_read_b64_tr_b16 %7, %11 offset:2048\n\t"
+               "s_waitcnt lgkmcnt(0)"
+               : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3]),
+                 "=&v"(x[4]), "=&v"(x[5]), "=&v"(x[6]), "=&v"(x[7])
+               : "v"(b1 + (cb0 ^ m1)), "v"(b1 + 512 + (cb0 ^ m1 ^ 16)),
+                 "v"(b1 + ((cb0 + 64) ^ m1)),
+                 "v"(b1 + 512 + ((cb0 + 64) ^ m1 ^ 16)));
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+      d[s][dt] = fa_join(x[4 * s + 2 * dt], x[4 * s + 2 * dt + 1]);
+}
+
+// dq kernel at D = 64, one BN-key tile, a 32-key group at a time: S^T and
+// dP^T of the group (4 k-steps each), dS rebuilt and packed in-register, then
+// dQ^T += K^T dS over the group's two 16-key slots.  Only 16 dS values are
+// live, so the tile length does not touch the register budget.  A group
+// wholly past the wave's causal diagonal (its first key > wave_last_key, the
+// last key the wave's last row sees) or past Skv has dS = 0 and is skipped,
+// wave-uniformly.
+template <int BN>
+DEV void fa_bwd_dq_tile_d64(bool boundary, const char* k_img,
+                            const char* v_img, const bf16x8 (&qreg)[4],
+                            const bf16x8 (&doreg)[4], f32x16 (&dq_acc)[2],
+                            int k0, int wave_last_key, int my_q, int S,
+                            int Skv, int diag, bool causal, float lse_q,
+                            float del_q, int lane) {
+  const int iq = lane & 31;
+  const int hi = lane >> 5;
+  const int bound = fa_mask_bound(k0 + 4 * hi, my_q, S, Skv, diag, causal);
+#pragma unroll
+  for (int g = 0; g < BN / 32; ++g) {
+    if (k0 + 32 * g > wave_last_key) break;
+    f32x16 sa, da;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int off = fa_swz_rm64t(32 * g + iq, kk * 32 + hi * 16);
+      bf16x8 kf = *reinterpret_cast<const bf16x8*>(k_img + off);
+      bf16x8 vf = *reinterpret_cast<const bf16x8*>(v_img + off);
+      sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qreg[kk], sa, 0, 0, 0);
+      da = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, doreg[kk], da, 0, 0,
+                                                   0);
+    }
+    float ds[16];
+    if (boundary) {
+      FA_BWD_DQ_DS_MASKED(ds, sa, da, 32 * g, bound, lse_q, del_q)
+    } else {
+      FA_BWD_DQ_DS_PLAIN(ds, sa, da, lse_q, del_q)
+    }
+    bf16x8 kt[2][2];
+    fa_tr_rm64t_2x2(kt, k_img, 32 * g, lane);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bf16x8 dsf = fa_pack_frag(ds, s * 8);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+        dq_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            kt[s][dt], dsf, dq_acc[dt], 0, 0, 0);
+    }
+  }
+}
+
+// dkv kernel at D = 64, one 32-q group (rows 32 sub .. of the tile's images,
+// first row qs0) for the wave's 32 exclusive keys.  The products are taken
+// the other way round than at D = 128: S = Q K_s^T and dP = dO V^T with the
+// wave's K and V rows as register B-fragments, so a lane owns its KEY column
+// and its registers run over q.  P and dS are then packed in-register
+// (fa_pack_frag) into B-fragments with own = key, k = q, and
+// dV^T += dO^T P, dK^T += Q^T dS take dO^T / Q^T from the images by
+// transposed reads.  No P / dS image, no LDS store: the tile reads 8 b128 and
+// 16 tr_b16 per 16 MFMAs.  The price is that lse / delta are per register,
+// not per lane: they come from the tile's LDS rows (lse_s / del_s, staged
+// with the images) as 16-B reads that all lanes of a half wave take from one
+// address (a broadcast).  The accumulators are dK^T / dV^T[d][own key], the
+// layout of the forward's O^T.  Every tile is masked, as at D = 128.
+DEV void fa_bwd_dkv_tile_d64(const char* q_img, const char* do_img,
+                             const float* lse_s, const float* del_s,
+                             const bf16x8 (&kreg)[4], const bf16x8 (&vreg)[4],
+                             f32x16 (&dk_acc)[2], f32x16 (&dv_acc)[2],
+                             int sub, int qs0, int my_key, int S, int Skv,
+                             int diag, bool causal, int lane) {
+  const int iq = lane & 31;        // A: own q row; B and C: own key column
+  const int hi = lane >> 5;
+  f32x16 sa, da;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const int off = fa_swz_rm64t(32 * sub + iq, kk * 32 + hi * 16);
+    bf16x8 qf = *reinterpret_cast<const bf16x8*>(q_img + off);
+    bf16x8 df = *reinterpret_cast<const bf16x8*>(do_img + off);
+    sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kreg[kk], sa, 0, 0, 0);
+    da = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, vreg[kk], da, 0, 0, 0);
+  }
+  // register r holds q = qs0 + 4 hi + fa_crow(r): unmasked iff
+  // q_lo <= fa_crow(r) <= q_hi (row tail and key tail above, causal below)
+  const int qrel = qs0 + 4 * hi;
+  const int q_hi = (my_key < Skv) ? S - 1 - qrel : -1;
+  const int q_lo = causal ? my_key - diag - qrel : 0;
+  float ps[16], ds[16];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float4 l4 =
+        *reinterpret_cast<const float4*>(lse_s + 32 * sub + 8 * g + 4 * hi);
+    const float4 d4 =
+        *reinterpret_cast<const float4*>(del_s + 32 * sub + 8 * g + 4 * hi);
+    const float lq[4] = {l4.x, l4.y, l4.z, l4.w};
+    const float dl[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = 4 * g + j;
+      const bool masked = (8 * g + j > q_hi) || (8 * g + j < q_lo);
+      const float pv = masked ? 0.f : __expf(sa[r] - lq[j]);
+      ps[r] = pv;                                       // P
+      ds[r] = masked ? 0.f : pv * (da[r] - dl[j]);      // dS (no scale)
+    }
+  }
+  bf16x8 dot[2][2], qt[2][2];
+  fa_tr_rm64t_2x2(dot, do_img, 32 * sub, lane);
+  fa_tr_rm64t_2x2(qt, q_img, 32 * sub, lane);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {        // k = q slices of 16
+    bf16x8 pf = fa_pack_frag(ps, s * 8);
+    bf16x8 dsf = fa_pack_frag(ds, s * 8);
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          dot[s][dt], pf, dv_acc[dt], 0, 0, 0);
+      dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          qt[s][dt], dsf, dk_acc[dt], 0, 0, 0);
+    }
+  }
+}
+
 // HETU_AMD_FA_MASK_ALL=1 runs the masked body on every tile (read at each
 // launch; for tests and for profiling both sides from one build)
 inline bool fa_mask_all() {
@@ -523,10 +756,10 @@ inline bool fa_mask_all() {
 void fa_delta_launch(const bf16* dO, const bf16* O, float* delta,
                      int64_t rows, int D, int H, int S, FaStrides so,
                      hipStream_t stream);
-// v2 forward over any layout; cu != nullptr selects the packed-varlen mode
-// (B = segments, S = Skv = max_seqlen, lse [H, lse_T]).
+// v2 forward over any layout, D = 64 or 128; cu != nullptr selects the
+// packed-varlen mode (B = segments, S = Skv = max_seqlen, lse [H, lse_T]).
 void fa2_fwd_launch(const bf16* q, const bf16* k, const bf16* v, bf16* o,
-                    float* lse, int B, int H, int Hkv, int S, int Skv,
+                    float* lse, int B, int H, int Hkv, int S, int Skv, int D,
                     float scale, bool causal, FaStrides sq, FaStrides skv,
                     FaStrides so, const int* cu, int lse_T,
                     hipStream_t stream);

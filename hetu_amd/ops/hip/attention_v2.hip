@@ -16,6 +16,15 @@
 //    4x4 hardware transpose read).
 //  * register staging (T14): issue next tile's global loads before compute,
 //    ds_write after the barrier; double-buffered LDS.
+//
+// D = 64 (fused-qkv and packed-varlen entries): the same skeleton over the
+// paged prefill kernel's geometry.  A K row is 128 B, so a 16 KiB image is a
+// 128-key tile: four 32-key blocks of S^T with 4 k-steps each (p[4][16]),
+// 4 q fragments, two 32-d accumulator tiles of O.  K is row-major with
+// fa_swz_rm_d<64> (derivation in attention_common.h), V in the
+// [key group][d subtile] image of fa_voff_d<64>, read a 32-key group at a
+// time by fa_tr_v2x2.  Ring, LDS size, NGLDS and the counted wait are the
+// D = 128 ones; the tile helpers count in BN keys.
 #include <torch/extension.h>
 #include "ext_stream.h"
 #include "attention_common.h"
@@ -23,12 +32,11 @@
 namespace {
 
 constexpr int BM = 256;       // q rows per workgroup (8 waves x 32)
-constexpr int BN = 64;        // kv tile
 constexpr int THREADS = FA_THREADS;   // one wave per 32 q rows
 constexpr int NGLDS = FA_KV_IMG / (THREADS * 16);  // glds per lane per image
 constexpr int NBUF = FA_RING; // KV ring depth (counted-vmcnt pipelining)
 
-template <int D>  // D = head dim (128)
+template <int D>  // D = head dim (64 or 128)
 // 96 KiB LDS -> one workgroup per CU regardless; a 2-block register cap
 // would only force tighter allocation for a block that cannot schedule
 __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
@@ -37,7 +45,11 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
     float* __restrict__ LSE, int B, int H, int Hkv, int S, int Skv,
     float scale, bool causal, FaStrides sq, FaStrides skv, FaStrides so,
     const int* __restrict__ cu, int lse_T, bool mask_all) {
-  static_assert(D == 128, "fa2 fwd: D=128 only");
+  static_assert(D == 64 || D == 128, "fa2 fwd: head dim");
+  constexpr int BN = FA_KV_IMG / (2 * D);   // kv tile: 64 keys (D = 128) / 128
+  constexpr int NG = BN / 32;               // 32-key blocks of S^T per tile
+  constexpr int NKK = D / 16;               // k-steps of S^T
+  constexpr int NDT = D / 32;               // 32-d accumulator tiles of O
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int b) -> char* { return smem + b * FA_KV_IMG; };
   auto v_lds = [&](int b) -> char* { return smem + (NBUF + b) * FA_KV_IMG; };
@@ -80,8 +92,9 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
 
   // ---- Q -> registers, prescaled by softmax scale --------------------
   // lane holds Q[my_q][16*kk + 8*hi .. +8) for kk = 0..7
-  bf16x8 qreg[8];
-  fa_load_row_frags(qreg, Qb + (int64_t)min(my_q, S - 1) * sq.rs, hi, scale);
+  bf16x8 qreg[NKK];
+  fa_load_row_frags_d<D>(qreg, Qb + (int64_t)min(my_q, S - 1) * sq.rs, hi,
+                         scale);
 
   // ---- staging: global_load_lds DMA, swizzle folded into the SOURCE
   // address (rule 21: glds writes lane-linear, dest = base + lane*16).
@@ -93,33 +106,35 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
   //   V ([kb][db] subtiles of [32key][16d]): subtile = pos>>10,
   //     key = (subtile>>3)*32 + ((pos>>5)&31),
   //     d = (subtile&7)*16 + ((pos>>4)&1)*8
+  // At D = 64 a K row is pos>>7 and a key group has 4 d-subtiles.
   const int wlane16 = lane * 16;
 #define ISSUE_GLDS(k0, buf)                                                 \
   do {                                                                      \
     _Pragma("unroll")                                                       \
     for (int i = 0; i < NGLDS; ++i) {                                       \
       int pos = (wid * NGLDS + i) * 1024 + wlane16;                         \
-      fa_glds16(Kb + (int64_t)min((k0) + (pos >> 8), Skv - 1) * skv.rs      \
-                    + fa_rm_src_col(pos),                                   \
+      fa_glds16(Kb + (int64_t)min((k0) + (pos >> (D == 128 ? 8 : 7)),       \
+                                  Skv - 1) * skv.rs                         \
+                    + fa_rm_src_col_d<D>(pos),                              \
                 k_lds(buf) + pos);                                          \
       int st = pos >> 10;                                                   \
-      int vkey = (st >> 3) * 32 + ((pos >> 5) & 31);                        \
-      int vd = (st & 7) * 16 + ((pos >> 4) & 1) * 8;                        \
+      int vkey = (st >> (D == 128 ? 3 : 2)) * 32 + ((pos >> 5) & 31);       \
+      int vd = (st & (D / 16 - 1)) * 16 + ((pos >> 4) & 1) * 8;             \
       fa_glds16(Vb + (int64_t)min((k0) + vkey, Skv - 1) * skv.rs + vd,      \
                 v_lds(buf) + pos);                                          \
     }                                                                       \
   } while (0)
 
   // ---- accumulators ---------------------------------------------------
-  f32x16 o_acc[4];                 // O^T[32*dt + crow(reg,hi)][q = iq]
+  f32x16 o_acc[NDT];               // O^T[32*dt + crow(reg,hi)][q = iq]
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
+  for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o_acc[dt][r] = 0.f;
   float m_i = -INFINITY, l_i = 0.f;
 
   const int wave_qmax = q0 + wid * 32 + 31;
-  const int n_tiles = fa_n_kv_tiles(q0, Skv, diag, causal);
+  const int n_tiles = fa_n_kv_tiles<BN>(q0, Skv, diag, causal);
 
   // prologue: tiles 0 and 1 in flight (3-deep ring, counted vmcnt:
   // per wave each tile is 2*NGLDS glds; waiting vmcnt(2*NGLDS) at the
@@ -142,7 +157,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
     // does this wave have any unmasked key in this tile?
     const bool active = !causal || (k0 <= wave_qmax + diag);
 
-    float p[2][16];                // P^T rows: p[ct][r] = P[q][32ct+crow]
+    float p[NG][16];               // P^T rows: p[ct][r] = P[q][32ct+crow]
     // mask + online softmax over p (all in-register; q = iq lane-local),
     // returns the O rescale.  MASK=false (interior tiles, see
     // fa_boundary_kv_tile) has no key index, no compare and no select
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
       if constexpr (MASK)
         bound = fa_mask_bound(k0 + 4 * hi, my_q, S, Skv, diag, causal);
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
+      for (int ct = 0; ct < NG; ++ct)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if constexpr (MASK)
@@ -169,7 +184,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
       m_i = mn;
       float psum = 0.f;
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
+      for (int ct = 0; ct < NG; ++ct)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float pv;
@@ -188,15 +203,15 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
     if (active) {
       // ---- S^T = K Q^T ------------------------------------------------
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
+      for (int ct = 0; ct < NG; ++ct) {
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
+        for (int kk = 0; kk < NKK; ++kk) {
           // A-frag: K rows 32*ct + (lane&31), d slice 16kk + 8hi..+8
           bf16x8 kf = *reinterpret_cast<const bf16x8*>(
-              k_lds(cur) + fa_swz_rm(32 * ct + iq, kk * 32 + hi * 16));
+              k_lds(cur) + fa_swz_rm_d<D>(32 * ct + iq, kk * 32 + hi * 16));
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qreg[kk], acc,
                                                         0, 0, 0);
         }
@@ -205,12 +220,12 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
       }
 
       const float alpha =
-          fa_boundary_kv_tile(wave_qmax - 31, k0, S, Skv, diag, causal,
-                              mask_all)
+          fa_boundary_kv_tile<BN>(wave_qmax - 31, k0, S, Skv, diag, causal,
+                                  mask_all)
               ? softmax(std::true_type{}) : softmax(std::false_type{});
       // rescale O^T
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
+      for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o_acc[dt][r] *= alpha;
 
@@ -222,15 +237,33 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
       // the tr_b16 read: each 4-lane cluster reads a [4 key][4 d] tile;
       // lane (4c + j) supplies &V[key_base + j][d_base(cluster)] (8 B,
       // 4 contiguous d), lane (4c + k) receives column k = its own d.
+      if constexpr (D == 128) {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8 pfrag = fa_pack_frag(p[ks >> 1], (ks & 1) * 8);
-        bf16x8 vf[4];
-        fa_tr_v4(vf, v_lds(cur), ks, lane);
+        for (int ks = 0; ks < 4; ++ks) {
+          bf16x8 pfrag = fa_pack_frag(p[ks >> 1], (ks & 1) * 8);
+          bf16x8 vf[4];
+          fa_tr_v4(vf, v_lds(cur), ks, lane);
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              vf[dt], pfrag, o_acc[dt], 0, 0, 0);
+          for (int dt = 0; dt < 4; ++dt)
+            o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                vf[dt], pfrag, o_acc[dt], 0, 0, 0);
+        }
+      } else {
+        // a 32-key group at a time: its two 16-key slots share one block
+        // of 8 transposed V reads
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          bf16x8 vf[2][2];
+          fa_tr_v2x2(vf, v_lds(cur), g, lane);
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            bf16x8 pfrag = fa_pack_frag(p[g], s * 8);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+              o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  vf[s][dt], pfrag, o_acc[dt], 0, 0, 0);
+          }
+        }
       }
     }
   }
@@ -240,7 +273,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
     float inv = (l_i > 0.f) ? 1.f / l_i : 0.f;
     bf16* orow = O + (cu ? (int64_t)row0 * so.rs : (int64_t)b * so.bs)
                  + (int64_t)h * so.hs + (int64_t)my_q * so.rs;
-    fa_store_row_bf16(o_acc, inv, orow, hi);
+    fa_store_row_bf16_d<D>(o_acc, inv, orow, hi);
     if (hi == 0) {
       int64_t li = cu ? ((int64_t)h * lse_T + row0 + my_q)
                       : ((int64_t)bh * S + my_q);
@@ -252,15 +285,17 @@ __global__ __launch_bounds__(THREADS, 1) void fa2_fwd_kernel(
 }  // namespace
 
 void fa2_fwd_launch(const bf16* q, const bf16* k, const bf16* v, bf16* o,
-                    float* lse, int B, int H, int Hkv, int S, int Skv,
+                    float* lse, int B, int H, int Hkv, int S, int Skv, int D,
                     float scale, bool causal, FaStrides sq, FaStrides skv,
                     FaStrides so, const int* cu, int lse_T,
                     hipStream_t stream) {
+  TORCH_CHECK(D == 64 || D == 128, "fa2 fwd: D must be 64 or 128, got ", D);
   const bool mask_all = fa_mask_all();
   dim3 grid(B * H, (S + BM - 1) / BM);
-  hipLaunchKernelGGL(fa2_fwd_kernel<128>, grid, dim3(THREADS), FA_FWD_LDS,
-                     stream, q, k, v, o, lse, B, H, Hkv, S, Skv, scale,
-                     causal, sq, skv, so, cu, lse_T, mask_all);
+  auto kernel = D == 128 ? fa2_fwd_kernel<128> : fa2_fwd_kernel<64>;
+  hipLaunchKernelGGL(kernel, grid, dim3(THREADS), FA_FWD_LDS, stream, q, k, v,
+                     o, lse, B, H, Hkv, S, Skv, scale, causal, sq, skv, so,
+                     cu, lse_T, mask_all);
 }
 
 // Packed-varlen entry (reference FlashAttention.cu mha_varlen_fwd): ONE
@@ -276,7 +311,8 @@ std::vector<torch::Tensor> flash_attn_varlen_fwd(
               cu.is_contiguous(), "varlen: cu int32 on device");
   const int T = q.size(0), H = q.size(1), D = q.size(2);
   const int Hkv = k.size(1);
-  TORCH_CHECK(D == 128, "fa2 varlen: D=128 only");
+  TORCH_CHECK(D == 64 || D == 128,
+              "fa2 varlen: D must be 64 or 128, got ", D);
   const int nseg = cu.numel() - 1;
   auto o = torch::empty_like(q);
   auto lse = torch::empty({H, (int64_t)T},
@@ -286,7 +322,7 @@ std::vector<torch::Tensor> flash_attn_varlen_fwd(
   fa2_fwd_launch((const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
                  (const bf16*)v.data_ptr(), (bf16*)o.data_ptr(),
                  lse.data_ptr<float>(), nseg, H, Hkv, (int)max_seqlen,
-                 (int)max_seqlen, (float)scale, causal, sq, skv, sq,
+                 (int)max_seqlen, D, (float)scale, causal, sq, skv, sq,
                  cu.data_ptr<int>(), T, hetu_current_stream());
   return {o, lse};
 }
@@ -299,7 +335,7 @@ std::vector<torch::Tensor> flash_attn_fwd_qkv(torch::Tensor qkv, int64_t H,
                                               bool causal, double scale) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous());
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "fa2 qkv: bf16 only");
-  TORCH_CHECK(D == 128, "fa2 qkv: D=128 only");
+  TORCH_CHECK(D == 64 || D == 128, "fa2 qkv: D must be 64 or 128, got ", D);
   const int B = qkv.size(0), S = qkv.size(1);
   const int64_t C = (H + 2 * Hkv) * D;
   TORCH_CHECK(qkv.size(2) == C, "qkv width mismatch");
@@ -310,7 +346,7 @@ std::vector<torch::Tensor> flash_attn_fwd_qkv(torch::Tensor qkv, int64_t H,
   FaStrides so{(long long)S * H * D, (long long)D, (long long)H * D};
   fa2_fwd_launch(base, base + H * D, base + (H + Hkv) * D,
                  (bf16*)o.data_ptr(), lse.data_ptr<float>(), B, H, Hkv, S, S,
-                 (float)scale, causal, sqkv, sqkv, so, nullptr, 0,
+                 (int)D, (float)scale, causal, sqkv, sqkv, so, nullptr, 0,
                  hetu_current_stream());
   return {o, lse};
 }
